@@ -8,7 +8,7 @@ buffer); the accumulators are summed once with an in-place RCCL all-reduce (insi
 cl2_reduce_accumulators) inside the timed region.  One "ray" = one closest-hit BVH query
 (SURVEY.md §8d); rays are counted on the device.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080] [--total-spp S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080] [--total-spp S] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -38,6 +38,10 @@ not read, against a level they are not served from, and is not a fraction of any
 scenes (cl2_tune) runs in the warm-up, never inside the clock.  `serial_run_sample_ms` times the reference's own loop --
 `run_sample()` then a read of the tone-mapped picture, every iteration (src/render.py:31-37).  `cpu_baseline` times the C
 oracle (CPU restatement of the reference's kernels, OpenMP over host cores) on a bounded sample.
+
+`--dump-outputs DIR` writes what the timed region handed its caller -- the accumulators after its last sample -- as DIR/<name>.npy
+(dump_outputs).  Scene, seed buffers and the samples run before the clock depend on the arguments alone, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -69,6 +73,9 @@ VALU_PEAK_GINST = 1024 * 2.4e9 / 2.0 / 1e9
 
 LINE_CAP = 4000            # characters of the ONE stdout line (the driver keeps 8,000 characters of stdout: BENCH_r05 lost its line to that)
 DETAIL_FILE = "bench_detail.json"
+DUMP_MAX_PIXELS = 1 << 20      # --dump-outputs: larger frames are written as a seeded sample of this many pixels (40 B each: 42 MB)
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20241015
 
 
 def _pick(d, keys):
@@ -177,6 +184,29 @@ def emit(out, stdout_fd=None):
     if stdout_fd is not None:
         os.dup2(stdout_fd, 1)
     print(text, flush=True)
+
+
+def dump_outputs(out_dir, r):
+    """`--dump-outputs DIR`: what a caller of the timed path receives -- the four accumulators of Renderer.read_accumulators() as the
+    timed region left them (sums over its samples, after the all-reduce when there is one) -- as DIR/<name>.npy, float32 (the
+    integer sample counts are exact in it).  Frames above DUMP_MAX_PIXELS pixels are written as a sample of pixels drawn with a
+    fixed seed (the same pixels for every array, every run and every build at that frame size): arrays of shape (n, channels)
+    in pixel order, and pixel_index.npy (float64) with each row's row-major pixel index.  Returns {name: shape}."""
+    import numpy as np
+    img, wts, cnt, uni = r.read_accumulators()
+    H, W = img.shape[:2]
+    arrays = {"summed_image": img, "summed_sample_weights": wts, "summed_sample_counts": cnt.astype(np.float32),
+              "unidirectional_image": uni}
+    if H * W > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, DUMP_MAX_PIXELS, replace=False))
+        arrays = {k: v.reshape(H * W, -1)[idx] for k, v in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def cpu_baseline(width, height, samples, repeats=2):
@@ -405,10 +435,11 @@ def _build_scene(name, W, H, builder=None, max_members=None):
     return s, desc + f", {len(s.triangles)} tris / {len(s.boxes)} boxes" + (f" (max_members {max_members})" if max_members is not None else "")
 
 
-def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world, with_comm, streams=1, order=0):
+def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world, with_comm, streams=1, order=0, dump_dir=None):
     """Warm-up (tuner + counting pass), the timed region, a serial per-stage breakdown.  `steps` = samples THIS
     rank renders inside the clock; with `streams` = K sample streams (cl2_set_sample_streams: K independent samples of the
-    frame per pass, one seed buffer each) that is ceil(steps / K) passes.  Returns the pieces of the JSON line that depend
+    frame per pass, one seed buffer each) that is ceil(steps / K) passes.  `dump_dir`: rank 0 writes the accumulators the
+    timed region left there (dump_outputs), before the breakdown adds to them.  Returns the pieces of the JSON line that depend
     on the workload."""
     import clive2_amd as c2  # noqa: F401
     from clive2_amd import _native
@@ -490,6 +521,7 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
     r_org = r.organisation()
     assert r_org["paths_share"] == org_before["paths_share"], "a tuning experiment ran inside the timed region"
     rays_local = c["rays"]
+    dumped = dump_outputs(dump_dir, r) if dump_dir and rank == 0 else None
     # untimed: per-stage breakdown (HIP events around every launch) over a few more samples, in serial
     # order on one stream -- with the sample pipeline on, spans of the two streams overlap and a
     # stage's span includes whatever ran beside it
@@ -613,7 +645,7 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
         roof["sample_streams"] = streams
         out = {"scene_desc": scene_desc, "rays_total": rays_total, "rays_local": rays_local, "dt": dt, "roofline": roof,
                "steps_total": int(steps_total), "steps_rank": steps, "tuner_samples_in_warmup": tuned * streams, "paths_share": org["paths_share"],
-               "comm": comm, "sample_streams": streams,
+               "comm": comm, "sample_streams": streams, "dumped": dumped,
                "stages": {k[3:]: round(cb[k] / n_break, 4) for k in cb if k.startswith("ms_")}}
     r.close()
     return out
@@ -868,7 +900,13 @@ def main():
     ap.add_argument("--cpu-samples", type=int, default=4)
     ap.add_argument("--spawn-timeout", type=float, default=1500.0, help="self-spawned ranks are ended after this many seconds")
     ap.add_argument("--dry-spawn", action="store_true", help="rank processes stop after the id hand-over and need no GPU (CPU test of the self-spawn path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the accumulators the timed region computed (after its last sample) to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.sample_streams < 1:
+        ap.error("--sample-streams must be at least 1")
+    if args.total_spp <= 0 and (args.steps < 1 or args.steps % args.sample_streams):
+        ap.error(f"--steps must be a positive multiple of --sample-streams ({args.sample_streams}): it is the number of timed samples")
     if args.debug_flags & 7:
         sys.exit("bench.py: debug bits 0-2 skip parts of the resolve stage (invalid renders); they exist only in the test "
                  "variant of the library and are refused here")
@@ -902,7 +940,7 @@ def main():
     else:
         my_steps = args.steps
     res = run_workload(args, args.scene, W, H, my_steps, args.warmup, rank, local_rank, world, with_comm=with_comm,
-                       streams=args.sample_streams)
+                       streams=args.sample_streams, dump_dir=args.dump_outputs)
     strong_leg = None
     # (CLIVE2_BENCH_FORCE_STRONG=1: rehearsal of this leg on a one-rank communicator -- a second communicator in the same
     # process after the first one was destroyed; not used by the driver)
@@ -958,6 +996,8 @@ def main():
             out["comm"] = res["comm"]
         if strong_leg:
             out["strong_scaling"] = strong_leg
+        if res["dumped"]:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": res["dumped"]}
         if world == 1 and not args.no_mesh:
             try:
                 out["serial_run_sample_ms"] = serial_loop(args.scene, W, H, local_rank)
