@@ -88,6 +88,7 @@ EXPORTS = [
     "cl2_tune", "cl2_set_subpath_gather", "cl2_comm_abort", "cl2_tone_log_sum", "cl2_tone_map",
     "cl2_set_sample_streams", "cl2_get_sample_streams", "cl2_set_export_stream", "cl2_comm_info",
     "cl2_read_walk_tallies", "cl2_set_reproducible", "cl2_get_reproducible", "cl2_set_traversal_order", "cl2_get_traversal_order",
+    "cl2_render_features", "cl2_read_features", "cl2_denoise",
 ]
 
 
@@ -152,6 +153,10 @@ def lib(variant=None):
         L.cl2_comm_info.argtypes = [C.c_void_p, C.POINTER(CommInfo)]
         L.cl2_tone_log_sum.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
         L.cl2_tone_map.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_size_t]
+        L.cl2_render_features.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        L.cl2_read_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        # the sigmas are C floats: without these argtypes ctypes would pass Python floats as doubles
+        L.cl2_denoise.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t]
         for name in ("cl2_reduce_accumulators", "cl2_comm_destroy", "cl2_comm_abort", "cl2_synchronize"):
             getattr(L, name).argtypes = [C.c_void_p]
         _libs[variant] = L

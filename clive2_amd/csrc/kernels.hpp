@@ -152,7 +152,9 @@ __global__ __launch_bounds__(BLOCK) void k_gen_light_rays(
 
 // ---------------------------------------------------------------- K2: generate_camera_rays
 // trace.metal:1020-1067 with indices[id] == id (renderer.py:92-94).
-__device__ __forceinline__ void gen_camera_ray(int id, const CameraRec& c, uint32_t& seed0, uint32_t& seed1, const PathBufs& pb) {
+// The ray of entry `id` alone: two draws of its xorshift state, the jittered film point and the direction to the focal
+// point.  Shared with the first-hit feature pass (denoise.hpp), which must cast exactly these rays.
+__device__ __forceinline__ void camera_ray(int id, const CameraRec& c, uint32_t& seed0, uint32_t& seed1, V3& origin, V3& dir) {
     const float x_offset = xorshift_random(seed0);
     const float y_offset = xorshift_random(seed1);
     const int pix = id % (c.pixel_width * c.pixel_height);          // the pixel of entry `id` (sample streams: see the header)
@@ -161,8 +163,13 @@ __device__ __forceinline__ void gen_camera_ray(int id, const CameraRec& c, uint3
     const float yn = (pixel_y + y_offset - 0.5f * c.pixel_height) / (float)c.pixel_height;
     const V3 xv = (xn * cam3(c.dx)) * c.phys_width;
     const V3 yv = (yn * cam3(c.dy)) * c.phys_height;
-    const V3 origin = (cam3(c.center) + xv) + yv;
-    const V3 dir = normalize(cam3(c.focal_point) - origin);
+    origin = (cam3(c.center) + xv) + yv;
+    dir = normalize(cam3(c.focal_point) - origin);
+}
+
+__device__ __forceinline__ void gen_camera_ray(int id, const CameraRec& c, uint32_t& seed0, uint32_t& seed1, const PathBufs& pb) {
+    V3 origin, dir;
+    camera_ray(id, c, seed0, seed1, origin, dir);
     const float c_imp = 1.0f / (c.phys_width * c.phys_height);
     pb.P0[id] = f4(origin, c_imp);
     pb.P1[id] = f4(dir, 1.0f);                    // l_importance "filled in later"

@@ -19,6 +19,7 @@
 
 #include "../../include/clive2_amd.h"
 #include "kernels.hpp"
+#include "denoise.hpp"
 #include "tonemap.hpp"
 #include "det_splat.hpp"
 #include "bvh_builder.hpp"
@@ -137,6 +138,17 @@ struct cl2_renderer {
     int comm_rank = 0, comm_nranks = 0;
     bool comm_poisoned = false;          // a collective failed or timed out (or the host said so): tear down with ncclCommAbort
     double* d_comm_scratch = nullptr;    // [COMM_SCRATCH] doubles for cl2_comm_allreduce_f64
+
+    // first-hit features and the denoiser (denoise.hpp): W x H entries each, allocated by the first cl2_render_features
+    uint2* d_feat_seeds = nullptr;       // private copy of the caller's seed buffer (d_seeds is never touched)
+    float4 *d_feat_o = nullptr, *d_feat_d = nullptr, *d_feat_hit = nullptr;
+    float4 *d_g0 = nullptr, *d_g1 = nullptr;   // {normal, depth}, {albedo b, g, r, coverage}
+    unsigned* d_feat_count = nullptr;    // [1] = W x H: the ray count of the traversal launches
+    unsigned* d_feat_work = nullptr;     // [WORK_STRIDE]: work counter of the 4-wide walk
+    Stats* d_feat_stats = nullptr;       // ray tally of the feature launches: kept apart from d_stats (cl2_read_counters)
+    bool features_valid = false;         // cleared by cl2_upload_scene
+    float4* d_dn[2] = {nullptr, nullptr};   // ping-pong colour of the filter passes
+    float* d_dn_out = nullptr;           // (H, W, 3) result of the last pass
 };
 
 namespace {
@@ -347,7 +359,11 @@ int ensure_wide_overflow(cl2_renderer* r) {
 }
 
 template <class Source>
-int launch_wide(cl2_renderer* r, hipStream_t st, int stage, const unsigned* count, unsigned* work_counter, Source src, int is_conn) {
+// quiet: the feature pass (denoise.hpp) -- the rays go to its own tally, not to cl2_read_counters / cl2_read_walk_tallies
+int launch_wide(cl2_renderer* r, hipStream_t st, int stage, const unsigned* count, unsigned* work_counter, Source src, int is_conn,
+                bool quiet = false) {
+    Stats* const stats = quiet ? r->d_feat_stats : r->d_stats;
+    const bool tally = !quiet && r->counting == 2;
     const int grid = stage == 0 ? persistent_grid_paths(r) : persistent_grid_conn(r);
     TRY(ensure_wide_overflow(r));
     WideView w = r->wide;
@@ -376,12 +392,12 @@ int launch_wide(cl2_renderer* r, hipStream_t st, int stage, const unsigned* coun
     BvhView b = r->bvh;
     b.n_lds_nodes = 0; b.lds_tris = 0; b.n_fast_nodes = 0;
 #define CL2_WIDE(REPS, TALLY, SPEC, PACK, ORDER) \
-    hipLaunchKernelGGL((k_traverse_wide<REPS, Source, TALLY, SPEC, PACK, ORDER>), dim3(grid), dim3(BLOCK), lds, st, w, b, count, work_counter, src, r->d_stats, is_conn)
+    hipLaunchKernelGGL((k_traverse_wide<REPS, Source, TALLY, SPEC, PACK, ORDER>), dim3(grid), dim3(BLOCK), lds, st, w, b, count, work_counter, src, stats, is_conn)
 // (a macro argument may not be a run-time value: one dispatch level per template parameter)
 #define CL2_WIDE_BY_SPEC(REPS, TALLY, PACK) do { if (spec) CL2_WIDE(REPS, TALLY, true, PACK, false); else CL2_WIDE(REPS, TALLY, false, PACK, false); } while (0)
 #define CL2_WIDE_BY_TALLY(REPS, PACK) do { \
-        if (r->traversal_order != 0) { if (r->counting == 2) CL2_WIDE(REPS, true, true, PACK, true); else CL2_WIDE(REPS, false, true, PACK, true); } \
-        else if (r->counting == 2) CL2_WIDE_BY_SPEC(REPS, true, PACK); else CL2_WIDE_BY_SPEC(REPS, false, PACK); } while (0)
+        if (r->traversal_order != 0) { if (tally) CL2_WIDE(REPS, true, true, PACK, true); else CL2_WIDE(REPS, false, true, PACK, true); } \
+        else if (tally) CL2_WIDE_BY_SPEC(REPS, true, PACK); else CL2_WIDE_BY_SPEC(REPS, false, PACK); } while (0)
     const bool spec = !((r->debug_flags >> 13) & 1);            // speculative expansion of the stack top (bvh_wide.hpp); bit 13: off
     // 36-byte triangle records, a pair fetched as one run of 72 bytes (bvh_wide.hpp: PACK); bit 14: the 48-byte records of the other
     // walks.  The opt-in nearest-first child order (cl2_set_traversal_order; NOT the parity path) exists for the speculative walk only.
@@ -869,6 +885,7 @@ int cl2_upload_scene(cl2_renderer* r, const void* boxes_v, int n_boxes, const vo
                      int n_mats, const void* camera_v, const void* light_tris_v, const float* light_areas,
                      const int32_t* light_tri_index, int light_count) {
     if (!r) return CL2_E_INVALID;
+    r->features_valid = false;           // the features describe the scene they were rendered from
     if (!boxes_v || !tris_v || !mats_v || !camera_v || !light_tris_v || !light_areas || !light_tri_index)
         return fail(r, CL2_E_INVALID, "NULL scene array");
     if (n_boxes < 1 || n_tris < 1 || light_count < 1) return fail(r, CL2_E_INVALID, "scene needs >=1 box, triangle and light");
@@ -2089,6 +2106,109 @@ int cl2_probe_traverse(cl2_renderer* r, const void* rays_v, size_t n_rays, int32
         }
     dev_free(r, d_o); dev_free(r, d_d); dev_free(r, d_h); dev_free(r, d_n);
     return rc;
+}
+
+// ---- first-hit features and the denoiser (denoise.hpp) ----
+int cl2_render_features(cl2_renderer* r, const uint32_t* seeds, size_t n_words, int samples) {
+    STAGE_PROLOGUE(r);
+    if (!seeds) return fail(r, CL2_E_INVALID, "NULL seed buffer");
+    if (n_words != 2 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "feature seeds: 2 words per pixel of the frame ((W*H, 2) uint32)");
+    if (samples < 1 || samples > 65536) return fail(r, CL2_E_INVALID, "feature samples must be in 1..65536");
+    const size_t FB = (size_t)r->FB;
+    if (!r->d_g0) {
+        int rc = dev_alloc(r, &r->d_feat_seeds, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_o, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_d, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_hit, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_count, (size_t)1);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_work, (size_t)WORK_STRIDE);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_stats, (size_t)1);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_g1, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_g0, FB);     // last: its presence says the set is complete
+        if (rc != CL2_OK) return rc;
+        const unsigned n = (unsigned)FB;
+        HIP_TRY(r, hipMemcpy(r->d_feat_count, &n, sizeof n, hipMemcpyHostToDevice));
+    }
+    r->features_valid = false;
+    hipStream_t st = r->stream;
+    HIP_TRY(r, hipMemcpyAsync(r->d_feat_seeds, seeds, FB * sizeof(uint2), hipMemcpyHostToDevice, st));
+    HIP_TRY(r, hipMemsetAsync(r->d_g0, 0, FB * sizeof(float4), st));
+    HIP_TRY(r, hipMemsetAsync(r->d_g1, 0, FB * sizeof(float4), st));
+    // the closest-hit dispatch of cl2_probe_traverse, in its uncounted form
+    const bool wide = r->traversal_mode == 5 && r->n_wide > 0 && !count_ref(r);
+    for (int k = 0; k < samples; k++) {
+        hipLaunchKernelGGL(k_feat_rays, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, r->cam, r->d_feat_seeds, r->d_feat_o, r->d_feat_d);
+        HIP_TRY(r, hipGetLastError());
+        if (wide) {
+            HIP_TRY(r, hipMemsetAsync(r->d_feat_work, 0, WORK_STRIDE * sizeof(unsigned), st));
+            PathRaySource src{nullptr, r->d_feat_o, r->d_feat_d, r->d_feat_hit};
+            TRY(launch_wide(r, st, 0, r->d_feat_count, r->d_feat_work, src, 0, true));
+        } else {
+            hipLaunchKernelGGL(k_traverse_paths<false>, dim3(grid_for(FB)), dim3(BLOCK), bvh_lds_bytes(r), st, r->bvh, (const int*)nullptr,
+                               r->d_feat_count, r->d_feat_o, r->d_feat_d, r->d_feat_hit, r->d_feat_stats);
+            HIP_TRY(r, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_feat_shade, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, r->d_feat_d, r->d_feat_hit, r->d_tri_shade,
+                           r->d_mats, r->d_g0, r->d_g1);
+        HIP_TRY(r, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_feat_finish, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, samples, r->d_g0, r->d_g1);
+    HIP_TRY(r, hipGetLastError());
+    TRY(drain(r));
+    r->features_valid = true;
+    return CL2_OK;
+}
+
+int cl2_read_features(cl2_renderer* r, float* g0, float* g1, size_t n_pixels) {
+    STAGE_PROLOGUE(r);
+    if (!g0 || !g1) return fail(r, CL2_E_INVALID, "NULL feature array");
+    if (n_pixels != (size_t)r->FB) return fail(r, CL2_E_INVALID, "feature arrays must hold W*H float4 entries");
+    if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipMemcpy(g0, r->d_g0, n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(r, hipMemcpy(g1, r->d_g1, n_pixels * sizeof(float4), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+
+int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* out_bgr,
+                size_t n_floats) {
+    STAGE_PROLOGUE(r);
+    if (!out_bgr) return fail(r, CL2_E_INVALID, "NULL output");
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "denoised picture must hold 3*W*H floats");
+    if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
+    auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
+    if (bad(sigma_color) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
+    if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
+    const size_t FB = (size_t)r->FB;
+    if (!r->d_dn_out) {
+        int rc = dev_alloc(r, &r->d_dn[0], FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_dn[1], FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_dn_out, 3 * FB);
+        if (rc != CL2_OK) return rc;
+    }
+    hipStream_t st = r->stream;
+    hipLaunchKernelGGL(k_denoise_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc, r->d_dn[0],
+                       iterations == 0 ? r->d_dn_out : (float*)nullptr);
+    HIP_TRY(r, hipGetLastError());
+    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
+    const float den_a = sigma_albedo * sigma_albedo;
+    for (int i = 0; i < iterations; i++) {
+        const int step = 1 << i;
+        const float den_c = std::ldexp(sigma_color * sigma_color, -2 * i);      // sigma_color^2 * 4^-i, exact scaling
+        const float4* cin = r->d_dn[i & 1];
+        float4* cout = r->d_dn[(i + 1) & 1];
+        float* out3 = i == iterations - 1 ? r->d_dn_out : nullptr;
+        if (step == 1)
+            hipLaunchKernelGGL(k_denoise_pass<1>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
+        else if (step == 2)
+            hipLaunchKernelGGL(k_denoise_pass<2>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
+        else
+            hipLaunchKernelGGL(k_denoise_pass<0>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
+        HIP_TRY(r, hipGetLastError());
+    }
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(out_bgr, r->d_dn_out, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 }  // extern "C"

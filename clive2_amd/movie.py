@@ -44,6 +44,9 @@ def main(argv=None):
     ap.add_argument("--out-root", type=str, default="../output")
     ap.add_argument("--host-tonemap", action="store_true",
                     help="tone-map every frame on the host with numpy (the reference's path, Renderer.image) instead of on the device")
+    ap.add_argument("--denoise", action="store_true",
+                    help="after each frame's samples, render its first-hit features and save the denoised picture (Renderer.denoised_image)")
+    ap.add_argument("--feature-samples", type=int, default=4, help="camera rays per pixel of the feature pass of --denoise")
     args = ap.parse_args(argv)
 
     rank, local_rank, world = rank_info()
@@ -65,7 +68,12 @@ def main(argv=None):
             renderer = Renderer(scene, device=0)     # the launcher exposes one GPU per rank: it is device 0
         renderer.run_samples(args.samples)
         # a frame leaves the device tone-mapped (6 MB at 1080p; Renderer.image reads 66 MB of accumulators and maps them with numpy)
-        save_frame(os.path.join(out_dir, f"frame_{f:04d}.png"), renderer.image if args.host_tonemap else renderer.tone_mapped("image"))
+        if args.denoise:
+            renderer.render_features(args.feature_samples)
+            image = renderer.denoised_image
+        else:
+            image = renderer.image if args.host_tonemap else renderer.tone_mapped("image")
+        save_frame(os.path.join(out_dir, f"frame_{f:04d}.png"), image)
         del renderer, scene
         print(f"Frame {f} time: {time.time() - t0:.3f}", flush=True)
     return 0

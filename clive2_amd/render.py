@@ -2,6 +2,7 @@
 instead of opening a cv2 window (display code is out of scope).
 
     python -m clive2_amd.render --scene empty --width 1280 --height 720 --samples 64 --out cornell.png
+    python -m clive2_amd.render --scene empty --samples 4 --denoise --out cornell_denoised.png
 
 Several GPUs: start one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE in the environment (e.g.
 `python -m torch.distributed.run --nproc-per-node N -m clive2_amd.render ...`; any spawner will do, torch
@@ -37,6 +38,9 @@ def main(argv=None):
     ap.add_argument("--reproducible", action="store_true",
                     help="sum the light image in a fixed order (Renderer.set_reproducible) instead of with float atomics: two runs "
                          "then write the same bytes, as the reference's sort + gather chain does (renderer.py:212-250); slower")
+    ap.add_argument("--denoise", action="store_true",
+                    help="after the samples, render the first-hit features and write the denoised picture (Renderer.denoised_image)")
+    ap.add_argument("--feature-samples", type=int, default=4, help="camera rays per pixel of the feature pass of --denoise")
     args = ap.parse_args(argv)
 
     rank, local_rank, world = rank_info()
@@ -87,7 +91,13 @@ def main(argv=None):
     # Tone-mapped uint8, BGR.  The film sits BEHIND the pinhole, so the picture on it is already upright
     # when read row 0 first (row 0 looks up at the ceiling light): the reference hands `renderer.image`
     # to cv2 unflipped (render.py:35-37).  Only the channel order changes for a PNG (BGR -> RGB).
-    image = renderer.tone_mapped("image") if args.device_tonemap else renderer.image
+    if args.denoise:
+        t1 = time.time()
+        renderer.render_features(args.feature_samples)
+        image = renderer.denoised_image
+        print(f"[rank {rank}] features ({args.feature_samples} rays per pixel) and denoising took {time.time() - t1:.2f} seconds")
+    else:
+        image = renderer.tone_mapped("image") if args.device_tonemap else renderer.image
     renderer.close()
     try:
         from PIL import Image

@@ -436,6 +436,45 @@ class Renderer:
                     "probe_traverse")
         return bi, bt, u, v
 
+    # ---- denoiser (cl2_render_features / cl2_read_features / cl2_denoise, csrc/denoise.hpp) ----
+    # settled on the Cornell box and the glass scene at 256 x 192, 4 samples, against 1024-sample pictures (include/clive2_amd.h)
+    DENOISE_DEFAULTS = dict(iterations=3, sigma_color=2.0, sigma_depth=0.1, sigma_albedo=0.1)
+
+    def render_features(self, samples=4, seeds=None):
+        """First-hit guide buffers of the frame: `samples` jittered camera rays per pixel, their closest hits averaged into
+        normal, depth, albedo and coverage (features()).  `seeds`: (W*H, 2) uint32 in the layout of set_seeds with one stream;
+        default make_seeds(W*H, seed=1), a buffer apart from the render's.  The render's seeds, accumulators and counters are
+        not touched."""
+        s = make_seeds(self.batch_size, seed=1) if seeds is None else seeds
+        s = np.ascontiguousarray(s, dtype=np.uint32)
+        if s.size != 2 * self.batch_size:
+            raise RendererError(f"feature seeds need {2 * self.batch_size} uint32 words, got {s.size}")
+        self._check(self._L.cl2_render_features(self._h, ptr(s), C.c_size_t(s.size), int(samples)), "cl2_render_features")
+
+    def features(self):
+        """The guide buffers the filter reads: normal (H,W,3), depth (H,W), albedo (H,W,3) b, g, r, coverage (H,W); float32."""
+        H, W = self.pixel_height, self.pixel_width
+        g0, g1 = np.empty((H, W, 4), np.float32), np.empty((H, W, 4), np.float32)
+        self._check(self._L.cl2_read_features(self._h, ptr(g0), ptr(g1), C.c_size_t(H * W)), "cl2_read_features")
+        return dict(normal=g0[..., :3], depth=g0[..., 3], albedo=g1[..., :3], coverage=g1[..., 3])
+
+    def denoised_radiance(self, iterations=None, sigma_color=None, sigma_depth=None, sigma_albedo=None):
+        """`radiance` after the edge-avoiding a-trous filter guided by the features (render_features() first; a new scene
+        needs new features): float32 (H,W,3), BGR.  Unset arguments take DENOISE_DEFAULTS."""
+        d = self.DENOISE_DEFAULTS
+        it = d["iterations"] if iterations is None else int(iterations)
+        sc = d["sigma_color"] if sigma_color is None else float(sigma_color)
+        sd = d["sigma_depth"] if sigma_depth is None else float(sigma_depth)
+        sa = d["sigma_albedo"] if sigma_albedo is None else float(sigma_albedo)
+        out = np.empty((self.pixel_height, self.pixel_width, 3), np.float32)
+        self._check(self._L.cl2_denoise(self._h, it, sc, sd, sa, ptr(out), C.c_size_t(out.size)), "cl2_denoise")
+        return out
+
+    @property
+    def denoised_image(self):
+        """`image` of the denoised radiance: tone_map(denoised_radiance(), exposure=4.0) on the host, uint8 (H,W,3), BGR."""
+        return tone_map(self.denoised_radiance(), exposure=4.0)
+
     def probe_math(self, which, x):
         """Device detmath / exact-reciprocal functions on a float32 array (`which`: sin cos acos atan exp asin rcp div_pi)."""
         code = ["sin", "cos", "acos", "atan", "exp", "asin", "rcp", "div_pi"].index(which)
