@@ -89,6 +89,8 @@ EXPORTS = [
     "cl2_set_sample_streams", "cl2_get_sample_streams", "cl2_set_export_stream", "cl2_comm_info",
     "cl2_read_walk_tallies", "cl2_set_reproducible", "cl2_get_reproducible", "cl2_set_traversal_order", "cl2_get_traversal_order",
     "cl2_render_features", "cl2_read_features", "cl2_denoise",
+    "cl2_set_error_tracking", "cl2_get_error_tracking", "cl2_read_moments_packed", "cl2_write_moments_packed",
+    "cl2_read_standard_error", "cl2_relative_error", "cl2_run_until",
 ]
 
 
@@ -157,6 +159,14 @@ def lib(variant=None):
         L.cl2_read_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         # the sigmas are C floats: without these argtypes ctypes would pass Python floats as doubles
         L.cl2_denoise.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t]
+        L.cl2_set_error_tracking.argtypes = [C.c_void_p, C.c_int]
+        L.cl2_get_error_tracking.argtypes = [C.c_void_p]
+        L.cl2_read_moments_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_write_moments_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_read_standard_error.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_relative_error.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double)]
+        L.cl2_run_until.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_double)]
         for name in ("cl2_reduce_accumulators", "cl2_comm_destroy", "cl2_comm_abort", "cl2_synchronize"):
             getattr(L, name).argtypes = [C.c_void_p]
         _libs[variant] = L

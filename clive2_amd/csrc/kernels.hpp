@@ -1147,46 +1147,85 @@ __device__ __forceinline__ float scrub(float x) {   // np.nan_to_num(x, posinf=0
 // next sample.
 // `FB` = pixels of the frame, `streams` = samples per pixel in this pass (entries s*FB + id): added in stream order, each
 // exactly as one process_images call adds one sample.
+//
+// MOMENTS = true (cl2_set_error_tracking, error_estimate.hpp): every addend also goes into the moment buffer mom [8][FB]:
+// with x_c the addend of acc row c (c = 0, 1, 2 = b, g, r), w that of row 3 and y = (x_b 0.0722 + x_g 0.7152) + x_r 0.2126
+// (float32, the luma of dn_compress), rows 0..2 += x_c x_c, 3 += w w, 4..6 += x_c w, 7 += y y -- one float32 add per row and
+// addend, in stream order.  MOMENTS = false is the default path and compiles to the same instructions as before the
+// template existed (`mom` is not read).
+template <bool MOMENTS>
+__device__ __forceinline__ void add_moments(float (&m)[8], float x0, float x1, float x2, float w) {
+    if constexpr (MOMENTS) {
+        const float y = (x0 * 0.0722f + x1 * 0.7152f) + x2 * 0.2126f;
+        m[0] += x0 * x0;
+        m[1] += x1 * x1;
+        m[2] += x2 * x2;
+        m[3] += w * w;
+        m[4] += x0 * w;
+        m[5] += x1 * w;
+        m[6] += x2 * w;
+        m[7] += y * y;
+    }
+}
+
+template <bool MOMENTS>
 __global__ __launch_bounds__(BLOCK) void k_accumulate(int FB, int streams, const float4* __restrict__ finalized,
                                                       const float* __restrict__ sample_w, float4* __restrict__ light_image,
-                                                      const float4* __restrict__ uni, float* __restrict__ acc) {
+                                                      const float4* __restrict__ uni, float* __restrict__ acc,
+                                                      float* __restrict__ mom) {
     const int id = blockIdx.x * BLOCK + threadIdx.x;
     if (id >= FB) return;
-    float a[8];
+    float a[8], m[8];
 #pragma unroll
     for (int c = 0; c < 8; c++) a[c] = acc[(size_t)c * FB + id];
+    if constexpr (MOMENTS) {
+#pragma unroll
+        for (int c = 0; c < 8; c++) m[c] = mom[(size_t)c * FB + id];
+    }
 #pragma unroll 1
     for (int s = 0; s < streams; s++) {
         const size_t e = (size_t)s * FB + id;
         const float4 f = finalized[e], l = light_image[e], u = uni[e];
-        a[0] += scrub(l.x + f.x);
-        a[1] += scrub(l.y + f.y);
-        a[2] += scrub(l.z + f.z);
-        a[3] += sample_w[e] + l.w;                      // K8's `sum_weights[id] += weight_sum`, :963
+        const float x0 = scrub(l.x + f.x), x1 = scrub(l.y + f.y), x2 = scrub(l.z + f.z);
+        const float w = sample_w[e] + l.w;              // K8's `sum_weights[id] += weight_sum`, :963
+        a[0] += x0;
+        a[1] += x1;
+        a[2] += x2;
+        a[3] += w;
         a[4] += scrub(u.x);
         a[5] += scrub(u.y);
         a[6] += scrub(u.z);
         a[7] += 1.0f;
+        add_moments<MOMENTS>(m, x0, x1, x2, w);
         light_image[e] = make_float4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int c = 0; c < 8; c++) acc[(size_t)c * FB + id] = a[c];
+    if constexpr (MOMENTS) {
+#pragma unroll
+        for (int c = 0; c < 8; c++) mom[(size_t)c * FB + id] = m[c];
+    }
 }
 
 // K6 + process_images in one launch for cl2_run_samples: the filtered sample goes straight from registers into the
 // accumulators (the per-sample images finalized / sample_weights are not written: they are what the stage calls
 // cl2_finalize_samples / cl2_process_images exchange, 36 B per pixel and a launch boundary per sample).
-// Same statements in the same order as k_finalize followed by k_accumulate.
+// Same statements in the same order as k_finalize followed by k_accumulate (moments included).
 // `B` = entries (streams x W x H, the stride of the aggregator rows); one thread per PIXEL adds its streams in order.
+template <bool MOMENTS>
 __global__ __launch_bounds__(BLOCK) void k_finalize_accumulate(int B, int W, int H, const float* __restrict__ agg,
                                                                float4* __restrict__ light_image, const float4* __restrict__ uni,
-                                                               float* __restrict__ acc) {
+                                                               float* __restrict__ acc, float* __restrict__ mom) {
     const int id = blockIdx.x * BLOCK + threadIdx.x;
     const int FB = W * H;
     if (id >= FB) return;
-    float a[8];
+    float a[8], m[8];
 #pragma unroll
     for (int c = 0; c < 8; c++) a[c] = acc[(size_t)c * FB + id];
+    if constexpr (MOMENTS) {
+#pragma unroll
+        for (int c = 0; c < 8; c++) m[c] = mom[(size_t)c * FB + id];
+    }
 #pragma unroll 1
     for (size_t base = 0; base < (size_t)B; base += (size_t)FB) {
         V3 total = v3(0, 0, 0);
@@ -1205,18 +1244,25 @@ __global__ __launch_bounds__(BLOCK) void k_finalize_accumulate(int B, int W, int
             }
         }
         const float4 l = light_image[base + id], u = uni[base + id];
-        a[0] += scrub(l.x + total.x);
-        a[1] += scrub(l.y + total.y);
-        a[2] += scrub(l.z + total.z);
-        a[3] += wsum + l.w;
+        const float x0 = scrub(l.x + total.x), x1 = scrub(l.y + total.y), x2 = scrub(l.z + total.z);
+        const float w = wsum + l.w;
+        a[0] += x0;
+        a[1] += x1;
+        a[2] += x2;
+        a[3] += w;
         a[4] += scrub(u.x);
         a[5] += scrub(u.y);
         a[6] += scrub(u.z);
         a[7] += 1.0f;
+        add_moments<MOMENTS>(m, x0, x1, x2, w);
         light_image[base + id] = make_float4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int c = 0; c < 8; c++) acc[(size_t)c * FB + id] = a[c];
+    if constexpr (MOMENTS) {
+#pragma unroll
+        for (int c = 0; c < 8; c++) mom[(size_t)c * FB + id] = m[c];
+    }
 }
 
 // ---------------------------------------------------------------- exactness self-test

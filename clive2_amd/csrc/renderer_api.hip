@@ -20,6 +20,7 @@
 #include "../../include/clive2_amd.h"
 #include "kernels.hpp"
 #include "denoise.hpp"
+#include "error_estimate.hpp"
 #include "tonemap.hpp"
 #include "det_splat.hpp"
 #include "bvh_builder.hpp"
@@ -149,6 +150,12 @@ struct cl2_renderer {
     bool features_valid = false;         // cleared by cl2_upload_scene
     float4* d_dn[2] = {nullptr, nullptr};   // ping-pong colour of the filter passes
     float* d_dn_out = nullptr;           // (H, W, 3) result of the last pass
+
+    // error tracking (cl2_set_error_tracking, error_estimate.hpp): second moments of the addends, [8][W*H], while tracking is on
+    float* d_mom = nullptr;
+    bool mom_valid = false;              // every addend in the accumulators also went into the moments
+    bool acc_clean = true;               // the accumulators hold nothing (cl2_create, cl2_reset_accumulators)
+    double* d_err_partial = nullptr;     // frame metric: [3][ERR_BLOCKS] per-workgroup partials + [4] result (first call)
 };
 
 namespace {
@@ -670,18 +677,29 @@ int launch_finalize(cl2_renderer* r, hipStream_t st) {
     return CL2_OK;
 }
 
+// with error tracking on (r->d_mom allocated) the <true> forms also add every addend's second moments
 int launch_accumulate(cl2_renderer* r, hipStream_t st) {
     Timed t(r, ST_ACCUMULATE, st);
-    hipLaunchKernelGGL(k_accumulate, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->FB, r->streams, r->d_finalized, r->d_sample_w,
-                       r->d_light_image, r->d_uni, r->d_acc);
+    if (r->d_mom)
+        hipLaunchKernelGGL(k_accumulate<true>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->FB, r->streams, r->d_finalized, r->d_sample_w,
+                           r->d_light_image, r->d_uni, r->d_acc, r->d_mom);
+    else
+        hipLaunchKernelGGL(k_accumulate<false>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->FB, r->streams, r->d_finalized, r->d_sample_w,
+                           r->d_light_image, r->d_uni, r->d_acc, (float*)nullptr);
+    r->acc_clean = false;
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
 }
 
 int launch_finalize_accumulate(cl2_renderer* r, hipStream_t st) {
     Timed t(r, ST_FINALIZE, st);
-    hipLaunchKernelGGL(k_finalize_accumulate, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg, r->d_light_image,
-                       r->d_uni, r->d_acc);
+    if (r->d_mom)
+        hipLaunchKernelGGL(k_finalize_accumulate<true>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
+                           r->d_light_image, r->d_uni, r->d_acc, r->d_mom);
+    else
+        hipLaunchKernelGGL(k_finalize_accumulate<false>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
+                           r->d_light_image, r->d_uni, r->d_acc, (float*)nullptr);
+    r->acc_clean = false;
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
 }
@@ -1510,6 +1528,9 @@ int cl2_reset_accumulators(cl2_renderer* r) {
     HIP_TRY(r, hipSetDevice(r->device));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     HIP_TRY(r, hipMemset(r->d_acc, 0, 8 * (size_t)r->FB * sizeof(float)));
+    if (r->d_mom) HIP_TRY(r, hipMemset(r->d_mom, 0, 8 * (size_t)r->FB * sizeof(float)));
+    r->mom_valid = r->d_mom != nullptr;
+    r->acc_clean = true;
     r->samples = 0;
     return CL2_OK;
 }
@@ -1523,7 +1544,12 @@ static int acc_copy(cl2_renderer* r, void* dst, const void* src, size_t n_floats
     return CL2_OK;
 }
 int cl2_read_accumulators_packed(cl2_renderer* r, float* dst, size_t n) { return acc_copy(r, dst, r ? r->d_acc : nullptr, n, hipMemcpyDeviceToHost); }
-int cl2_write_accumulators_packed(cl2_renderer* r, const float* src, size_t n) { return acc_copy(r, r ? r->d_acc : nullptr, src, n, hipMemcpyHostToDevice); }
+int cl2_write_accumulators_packed(cl2_renderer* r, const float* src, size_t n) {
+    TRY(acc_copy(r, r ? r->d_acc : nullptr, src, n, hipMemcpyHostToDevice));
+    r->acc_clean = false;
+    r->mom_valid = false;                // until cl2_write_moments_packed brings the moments that go with these sums
+    return CL2_OK;
+}
 
 // ---------------------------------------------------------------- output stage: tone map on the device (csrc/tonemap.hpp)
 namespace {
@@ -1707,12 +1733,26 @@ int cl2_reduce_accumulators(cl2_renderer* r) {
     RcclApi* api = rccl_api(why);
     if (!api) return fail(r, CL2_E_COMM, why);
     COMM_HIP_TRY(r, api, hipSetDevice(r->device));
+    // error tracking: every rank must issue the same collectives.  One small all-reduce (max over [t, -t]: the largest and the
+    // smallest t of the ranks) first, t = 0 tracking off, 1 on with invalid moments, 2 on with valid ones
+    const double t = r->d_mom ? (r->mom_valid ? 2.0 : 1.0) : 0.0;
+    double tt[2] = {t, -t};
+    TRY(cl2_comm_allreduce_f64(r, tt, 2, 1));
+    const double t_max = tt[0], t_min = -tt[1];
     {
         const int rc = drain(r);
         if (rc != CL2_OK) { r->comm_poisoned = true; comm_abort(r, api); return rc; }
     }
     COMM_RCCL_TRY(r, api, api->AllReduce(r->d_acc, r->d_acc, 8 * (size_t)r->FB, ncclFloat, ncclSum, r->comm, r->stream));
-    return comm_wait(r, api, "cl2_reduce_accumulators");
+    if (t_min >= 1.0)
+        COMM_RCCL_TRY(r, api, api->AllReduce(r->d_mom, r->d_mom, 8 * (size_t)r->FB, ncclFloat, ncclSum, r->comm, r->stream));
+    TRY(comm_wait(r, api, "cl2_reduce_accumulators"));
+    r->acc_clean = false;
+    r->mom_valid = t_min == 2.0;
+    if (t_min == 0.0 && t_max >= 1.0)
+        return fail(r, CL2_E_STATE, "error tracking is on on some ranks and off on others: the accumulators were reduced, the moments "
+                                    "are invalid on every rank (cl2_reset_accumulators makes them valid again)");
+    return CL2_OK;
 }
 
 /* n <= 16 host doubles, summed (op 0) or maximised (op 1) over the ranks, in place: barrier, the
@@ -2208,6 +2248,130 @@ int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
     }
     TRY(drain(r));
     HIP_TRY(r, hipMemcpy(out_bgr, r->d_dn_out, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+
+// ---------------------------------------------------------------- error estimates (csrc/error_estimate.hpp)
+namespace {
+int need_moments(cl2_renderer* r) {
+    if (!r->d_mom) return fail(r, CL2_E_STATE, "error tracking is off (cl2_set_error_tracking)");
+    if (!r->mom_valid)
+        return fail(r, CL2_E_STATE, "the moments do not cover every sample in the accumulators (tracking was switched on after samples, "
+                                    "or accumulators were written without their moments): cl2_reset_accumulators or cl2_write_moments_packed");
+    return CL2_OK;
+}
+
+// e(floor) of the current accumulators and moments, reduced on the device in a fixed order
+int eval_rel_error(cl2_renderer* r, double floor, double* out) {
+    if (!r->d_err_partial) TRY(dev_alloc(r, &r->d_err_partial, (size_t)3 * ERR_BLOCKS + 4));
+    const int grid = std::min(grid_for(r->FB), ERR_BLOCKS);
+    double* res = r->d_err_partial + 3 * ERR_BLOCKS;
+    hipLaunchKernelGGL(k_rel_error_partial, dim3(grid), dim3(256), 0, r->stream, r->FB, (const float*)r->d_acc, (const float*)r->d_mom,
+                       floor, r->d_err_partial);
+    hipLaunchKernelGGL(k_rel_error_final, dim3(1), dim3(256), 0, r->stream, (const double*)r->d_err_partial, grid, res);
+    HIP_TRY(r, hipGetLastError());
+    HIP_TRY(r, hipMemcpyAsync(out, res, sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    return CL2_OK;
+}
+}  // namespace
+
+int cl2_set_error_tracking(cl2_renderer* r, int on) {
+    if (!r) return CL2_E_INVALID;
+    if (on != 0 && on != 1) return fail(r, CL2_E_INVALID, "error tracking: 0 off, 1 on");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    if (!on) {
+        dev_free(r, r->d_mom);
+        r->mom_valid = false;
+        return CL2_OK;
+    }
+    if (r->d_mom) return CL2_OK;
+    TRY(dev_alloc(r, &r->d_mom, 8 * (size_t)r->FB));
+    HIP_TRY(r, hipMemset(r->d_mom, 0, 8 * (size_t)r->FB * sizeof(float)));
+    r->mom_valid = r->acc_clean;
+    return CL2_OK;
+}
+
+int cl2_get_error_tracking(const cl2_renderer* r) { return r ? (r->d_mom ? 1 : 0) : CL2_E_INVALID; }
+
+int cl2_read_moments_packed(cl2_renderer* r, float* dst, size_t n_floats) {
+    if (!r || !dst) return CL2_E_INVALID;
+    if (n_floats != 8 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed moments hold 8*W*H floats");
+    TRY(need_moments(r));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(dst, r->d_mom, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+
+int cl2_write_moments_packed(cl2_renderer* r, const float* src, size_t n_floats) {
+    if (!r || !src) return CL2_E_INVALID;
+    if (n_floats != 8 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed moments hold 8*W*H floats");
+    if (!r->d_mom) return fail(r, CL2_E_STATE, "error tracking is off (cl2_set_error_tracking)");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(r->d_mom, src, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    r->mom_valid = true;
+    return CL2_OK;
+}
+
+int cl2_read_standard_error(cl2_renderer* r, float* out, size_t n_floats) {
+    if (!r || !out) return CL2_E_INVALID;
+    if (n_floats != 4 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "the standard errors hold 4*W*H floats");
+    TRY(need_moments(r));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    float4* d = nullptr;
+    HIP_TRY(r, hipMalloc(&d, (size_t)r->FB * sizeof(float4)));
+    hipLaunchKernelGGL(k_standard_error, dim3((r->FB + 255) / 256), dim3(256), 0, r->stream, r->FB, (const float*)r->d_acc,
+                       (const float*)r->d_mom, d);
+    int rc = hipGetLastError() == hipSuccess ? CL2_OK : fail(r, CL2_E_HIP, "k_standard_error launch failed");
+    if (rc == CL2_OK && hipStreamSynchronize(r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "k_standard_error failed");
+    if (rc == CL2_OK && hipMemcpy(out, d, n_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(r, CL2_E_HIP, "standard error download failed");
+    (void)hipFree(d);
+    return rc;
+}
+
+int cl2_relative_error(cl2_renderer* r, double floor, double* out) {
+    if (!r || !out) return CL2_E_INVALID;
+    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
+    TRY(need_moments(r));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    return eval_rel_error(r, floor, out);
+}
+
+int cl2_run_until(cl2_renderer* r, double target, double floor, int min_passes, int max_passes, int check_every, int* passes_done,
+                  double* error_out) {
+    if (!r) return CL2_E_INVALID;
+    if (passes_done) *passes_done = 0;
+    if (!(target > 0.0) || !std::isfinite(target)) return fail(r, CL2_E_INVALID, "target must be > 0 and finite");
+    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
+    if (check_every < 1) return fail(r, CL2_E_INVALID, "check_every must be >= 1");
+    if (max_passes < 1 || min_passes < 0 || min_passes > max_passes) return fail(r, CL2_E_INVALID, "need 0 <= min_passes <= max_passes, max_passes >= 1");
+    STAGE_PROLOGUE(r);
+    TRY(need_moments(r));
+    int done = 0;
+    double e = std::numeric_limits<double>::infinity();
+    bool evaluated = false;
+    if (min_passes > 0) {
+        TRY(cl2_run_samples(r, min_passes));
+        done = min_passes;
+        if (passes_done) *passes_done = done;
+    }
+    while (done < max_passes) {
+        const int chunk = std::min(check_every, max_passes - done);
+        TRY(cl2_run_samples(r, chunk));
+        done += chunk;
+        if (passes_done) *passes_done = done;
+        TRY(eval_rel_error(r, floor, &e));
+        evaluated = true;
+        if (e <= target) break;
+    }
+    if (!evaluated) TRY(eval_rel_error(r, floor, &e));
+    if (error_out) *error_out = e;
     return CL2_OK;
 }
 

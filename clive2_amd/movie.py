@@ -16,7 +16,7 @@ import time
 import numpy as np
 
 from .distributed import rank_info
-from .renderer import Renderer, RendererError
+from .renderer import ERROR_FLOOR, Renderer, RendererError
 from .scene import create_scene_from_preset_with_params
 
 
@@ -47,7 +47,18 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true",
                     help="after each frame's samples, render its first-hit features and save the denoised picture (Renderer.denoised_image)")
     ap.add_argument("--feature-samples", type=int, default=4, help="camera rays per pixel of the feature pass of --denoise")
+    ap.add_argument("--target-error", type=float, default=None,
+                    help="render each frame until its relative error (Renderer.relative_error) is at most this, --samples as the cap")
+    ap.add_argument("--error-floor", type=float, default=None,
+                    help=f"floor of the relative error's denominator L + floor (default {ERROR_FLOOR})")
+    ap.add_argument("--check-every", type=int, default=8, help="passes between two checks of --target-error")
     args = ap.parse_args(argv)
+    if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
+        ap.error("--target-error must be positive and finite")
+    if args.error_floor is not None and not (args.error_floor >= 0 and np.isfinite(args.error_floor)):
+        ap.error("--error-floor must be >= 0 and finite")
+    if args.check_every < 1:
+        ap.error("--check-every must be >= 1")
 
     rank, local_rank, world = rank_info()
     out_dir = os.path.join(args.out_root, args.movie_name)
@@ -66,7 +77,12 @@ def main(argv=None):
             if local_rank == 0:
                 raise
             renderer = Renderer(scene, device=0)     # the launcher exposes one GPU per rank: it is device 0
-        renderer.run_samples(args.samples)
+        note = ""
+        if args.target_error is not None:
+            _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every)
+            note = f" ({renderer.samples} samples, relative error {reached:.4g})"
+        else:
+            renderer.run_samples(args.samples)
         # a frame leaves the device tone-mapped (6 MB at 1080p; Renderer.image reads 66 MB of accumulators and maps them with numpy)
         if args.denoise:
             renderer.render_features(args.feature_samples)
@@ -75,7 +91,7 @@ def main(argv=None):
             image = renderer.image if args.host_tonemap else renderer.tone_mapped("image")
         save_frame(os.path.join(out_dir, f"frame_{f:04d}.png"), image)
         del renderer, scene
-        print(f"Frame {f} time: {time.time() - t0:.3f}", flush=True)
+        print(f"Frame {f} time: {time.time() - t0:.3f}{note}", flush=True)
     return 0
 
 

@@ -3,6 +3,7 @@ instead of opening a cv2 window (display code is out of scope).
 
     python -m clive2_amd.render --scene empty --width 1280 --height 720 --samples 64 --out cornell.png
     python -m clive2_amd.render --scene empty --samples 4 --denoise --out cornell_denoised.png
+    python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --error-out err.npy
 
 Several GPUs: start one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE in the environment (e.g.
 `python -m torch.distributed.run --nproc-per-node N -m clive2_amd.render ...`; any spawner will do, torch
@@ -16,7 +17,7 @@ import numpy as np
 
 from . import _native
 from .distributed import rank_info, samples_for_rank, join_communicator
-from .renderer import Renderer, RendererError, stream_seeds
+from .renderer import ERROR_FLOOR, Renderer, RendererError, stream_seeds
 from .scene import create_scene_from_preset
 
 
@@ -41,9 +42,26 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true",
                     help="after the samples, render the first-hit features and write the denoised picture (Renderer.denoised_image)")
     ap.add_argument("--feature-samples", type=int, default=4, help="camera rays per pixel of the feature pass of --denoise")
+    ap.add_argument("--target-error", type=float, default=None,
+                    help="render until the relative error e (Renderer.relative_error) is at most this, with --samples as the cap "
+                         "(one rank only)")
+    ap.add_argument("--error-floor", type=float, default=None,
+                    help=f"floor of the relative error's denominator L + floor (default {ERROR_FLOOR})")
+    ap.add_argument("--check-every", type=int, default=8, help="passes between two checks of --target-error")
+    ap.add_argument("--error-out", type=str, default=None,
+                    help="save the per-pixel standard error (Renderer.standard_error: (H, W, 4) float32 b, g, r, luma) as .npy")
     args = ap.parse_args(argv)
+    # refused before any renderer is made
+    if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
+        ap.error("--target-error must be positive and finite")
+    if args.error_floor is not None and not (args.error_floor >= 0 and np.isfinite(args.error_floor)):
+        ap.error("--error-floor must be >= 0 and finite")
+    if args.check_every < 1:
+        ap.error("--check-every must be >= 1")
 
     rank, local_rank, world = rank_info()
+    if args.target_error is not None and world > 1:
+        ap.error("--target-error renders one frame on one GPU: run it with a single rank (WORLD_SIZE=1)")
     scene = create_scene_from_preset(args.scene, pixel_width=args.width, pixel_height=args.height)
     if world > 1:
         # one GPU per rank; a launcher that exposes a single GPU to each rank makes it device 0
@@ -54,14 +72,21 @@ def main(argv=None):
     K = renderer.streams
     if args.reproducible:
         renderer.set_reproducible(True)
+    if args.target_error is not None or args.error_out:
+        renderer.set_error_tracking(True)
     # seed buffers of the job: stream k of rank r is buffer r * K + k
     renderer.set_seeds(stream_seeds(args.width * args.height, K, first_rank=rank * K))
     if world > 1:
         join_communicator(renderer, rank, world)
     t0 = time.time()
     failure = None
+    reached = None
     try:
-        renderer.run_samples(-(-samples_for_rank(args.samples, rank, world) // K))
+        if args.target_error is not None:
+            _, reached = renderer.render_until(args.target_error, max(1, -(-args.samples // K)), floor=args.error_floor,
+                                               check_every=args.check_every)
+        else:
+            renderer.run_samples(-(-samples_for_rank(args.samples, rank, world) // K))
     except (KeyboardInterrupt, RendererError) as e:
         failure = e
     if world > 1:
@@ -85,6 +110,10 @@ def main(argv=None):
     dt = time.time() - t0
     rays = renderer.counters()["rays"]
     print(f"[rank {rank}] rendering took {dt:.2f} seconds ({renderer.samples} samples, {rays / max(dt, 1e-9) / 1e6:.0f} Mrays/s)")
+    if reached is not None:
+        print(f"[rank {rank}] target error {args.target_error}: {renderer.samples} samples, relative error {reached:.4g}")
+    if args.error_out and rank == 0:
+        np.save(args.error_out, renderer.standard_error())
     if rank != 0:
         renderer.close()
         return 0

@@ -27,6 +27,11 @@ from .constants import timed, MAX_PATH_LENGTH  # noqa: F401
 
 LIGHT, CAMERA = 0, 1
 
+# Default floor of the relative error e(floor) = sqrt(mean var_L / (L + floor)^2) (Renderer.relative_error): half the darkest
+# percentile of the Cornell box's and the glass scene's luma (0.0022), so it keeps truly near-black pixels from dominating e and
+# leaves it a relative error everywhere else
+ERROR_FLOOR = 0.001
+
 
 def make_seeds(batch_size, seed=20240928, rank=0):
     """Seed buffer of SURVEY.md §8(d): `RandomState(seed+rank).randint(0, 2**32, (B,2), uint32)`
@@ -474,6 +479,58 @@ class Renderer:
     def denoised_image(self):
         """`image` of the denoised radiance: tone_map(denoised_radiance(), exposure=4.0) on the host, uint8 (H,W,3), BGR."""
         return tone_map(self.denoised_radiance(), exposure=4.0)
+
+    # ---- error estimates (cl2_set_error_tracking ... cl2_run_until, csrc/error_estimate.hpp) ----
+    ERROR_FLOOR = ERROR_FLOOR
+
+    def set_error_tracking(self, on=True):
+        """Track the second moments of every sample's addends (off by default; 32*W*H bytes of device memory while on).  Turned
+        on while the accumulators hold samples, the moments stay invalid -- and the error calls refuse -- until reset_accumulators()."""
+        self._check(self._L.cl2_set_error_tracking(self._h, int(bool(on))), "cl2_set_error_tracking")
+
+    @property
+    def error_tracking(self):
+        return bool(self._L.cl2_get_error_tracking(self._h) == 1)
+
+    def moments(self):
+        """The moment buffer [8][W*H] float32 (x_c^2 b, g, r | w^2 | x_c w b, g, r | y^2), packed like packed_accumulators()."""
+        a = np.empty(8 * self.batch_size, np.float32)
+        self._check(self._L.cl2_read_moments_packed(self._h, ptr(a), C.c_size_t(a.size)), "cl2_read_moments_packed")
+        return a
+
+    def load_moments(self, a):
+        """Write the moment buffer (checkpoints: after load_packed_accumulators, which invalidates the moments)."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        self._check(self._L.cl2_write_moments_packed(self._h, ptr(a), C.c_size_t(a.size)), "cl2_write_moments_packed")
+
+    def standard_error(self):
+        """Per-pixel standard error of `radiance` by the delta method: float32 (H,W,4) b, g, r, luma; 0 where the pixel has no
+        sample weight, inf with fewer than 2 samples."""
+        out = np.empty((self.pixel_height, self.pixel_width, 4), np.float32)
+        self._check(self._L.cl2_read_standard_error(self._h, ptr(out), C.c_size_t(out.size)), "cl2_read_standard_error")
+        return out
+
+    def relative_error(self, floor=None):
+        """e(floor) = sqrt(mean over covered pixels of var_L / (L + floor)^2): the frame's relative noise level."""
+        e = C.c_double(0.0)
+        f = self.ERROR_FLOOR if floor is None else float(floor)
+        self._check(self._L.cl2_relative_error(self._h, f, C.byref(e)), "cl2_relative_error")
+        return e.value
+
+    def render_until(self, target, max_samples, floor=None, min_samples=2, check_every=8):
+        """Render until relative_error(floor) <= target, at most `max_samples` passes (units of run_samples: a pass renders
+        one sample per stream): first `min_samples`, then chunks of `check_every`, checking after each.  Turns error tracking on
+        if it is off.  Returns (passes rendered, error reached)."""
+        if not self.error_tracking:
+            self.set_error_tracking(True)
+        f = self.ERROR_FLOOR if floor is None else float(floor)
+        done, e = C.c_int(0), C.c_double(0.0)
+        try:
+            self._check(self._L.cl2_run_until(self._h, float(target), f, int(min_samples), int(max_samples), int(check_every),
+                                              C.byref(done), C.byref(e)), "cl2_run_until")
+        finally:
+            self.samples += done.value * self.streams
+        return done.value, e.value
 
     def probe_math(self, which, x):
         """Device detmath / exact-reciprocal functions on a float32 array (`which`: sin cos acos atan exp asin rcp div_pi)."""

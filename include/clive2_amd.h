@@ -211,6 +211,11 @@ int cl2_synchronize(cl2_renderer* r);                /* drains the handle's stre
 int cl2_comm_unique_id_bytes(void);
 int cl2_comm_get_unique_id(void* out_id, size_t n_bytes);           /* error text: cl2_last_error(NULL) */
 int cl2_comm_init_rank(cl2_renderer* r, int nranks, int rank, const void* unique_id, size_t n_bytes);
+/* With error tracking (cl2_set_error_tracking) the moment buffer is reduced too.  So that ranks which disagree never issue
+ * different collectives, the call first all-reduces every rank's tracking state (cl2_comm_allreduce_f64, op max over [t, -t]):
+ * one small collective more than the accumulators' all-reduce, whether tracking is on or not.  If tracking is on on some ranks
+ * and off on others, the accumulators are reduced as usual, the moments are marked invalid everywhere and the call returns
+ * CL2_E_STATE; moments invalid on any rank are invalid on every rank after the sum. */
 int cl2_reduce_accumulators(cl2_renderer* r);
 /* n <= 16 host doubles, in place, op 0 = sum, 1 = max over the ranks: barrier, max-over-ranks clock,
  * whole-job ray tally, error-flag agreement before the collective */
@@ -383,6 +388,45 @@ int cl2_read_features(cl2_renderer* r, float* g0, float* g1, size_t n_pixels);
  * sigmas positive and finite.  CL2_E_STATE without current features (none rendered, or a scene uploaded since). */
 int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* out_bgr,
                 size_t n_floats);
+
+/* -- error estimates: per-pixel standard errors and "render until the noise is below X" (csrc/error_estimate.hpp).  No
+ *    reference counterpart.
+ *
+ * An ADDEND is what one sample stream of one pass adds to one pixel: x_c = the value added to accumulator row c (c = 0, 1, 2 =
+ * b, g, r: scrub(light + finalized)), w = the value added to row 3 (sample weight + light weight), and
+ * y = (x_b 0.0722 + x_g 0.7152) + x_r 0.2126 (float32).  While tracking is on, a moment buffer [8][W*H] of float32 sums gets
+ *     x_c^2 (rows 0..2), w^2 (3), x_c w (4..6), y^2 (7)
+ * from every addend, in stream order, one float32 add per row (the kernels are built with -ffp-contract=off).
+ * The picture is the ratio Sum x / Sum w; its per-pixel standard error by the delta method (float64), n = acc row 7:
+ *     Wt = acc row 3 not finite or <= 0: uncovered, 0 and not part of the frame metric;  n < 2: +inf;
+ *     else I_c = X_c / Wt,  S_c = max(0, m_c - 2 I_c m_{4+c} + I_c^2 m_3),  var_c = n S_c / ((n - 1) Wt^2),
+ *     luma likewise from L = luma(I), m_7 and luma(m_4, m_5, m_6).
+ * Frame metric e(floor) = sqrt((1/N) sum_covered var_L / (L + floor)^2) over the N covered pixels (+inf if N = 0 or a covered
+ * pixel has n < 2; a pixel with var_L = 0 adds 0), reduced in a fixed order on the device: the same bytes on every call.
+ *
+ * Tracking is off by default; with it off every kernel runs exactly the code it runs without this feature.  Turning it on
+ * allocates and zeroes the moment buffer (32 W H bytes of device memory: 66 MB at 1080p) and costs the accumulation one more
+ * read and write of it per pass; turning it off frees it.  The moments are VALID when every addend in the accumulators also
+ * went into them: cl2_reset_accumulators zeroes them and makes them valid; turning tracking on while the accumulators hold
+ * samples, or cl2_write_accumulators_packed, leaves them invalid until a reset (or, after a write, cl2_write_moments_packed).
+ * Every call below but the first two returns CL2_E_STATE while tracking is off or the moments are invalid (writing needs
+ * tracking on only). -- */
+int cl2_set_error_tracking(cl2_renderer* r, int on);
+int cl2_get_error_tracking(const cl2_renderer* r);
+/* the moment buffer [8][W*H] as host floats, for checkpoints and tests (n_floats = 8*W*H); writing makes the moments valid */
+int cl2_read_moments_packed(cl2_renderer* r, float* host_dst, size_t n_floats);
+int cl2_write_moments_packed(cl2_renderer* r, const float* host_src, size_t n_floats);
+/* (H, W, 4) float32 standard errors b, g, r, luma (n_floats = 4*W*H) */
+int cl2_read_standard_error(cl2_renderer* r, float* out, size_t n_floats);
+/* e(floor), floor >= 0 and finite */
+int cl2_relative_error(cl2_renderer* r, double floor, double* out);
+/* Renders until e(floor) <= target.  Units are passes, as for cl2_run_samples(n): first min_passes, then chunks of check_every
+ * (the last one clipped to max_passes), each through cl2_run_samples; after each chunk e(floor) is evaluated on the device, and
+ * the call stops at the first chunk boundary with e <= target, or at max_passes.  *passes_done = passes rendered (also when the
+ * call fails part way), *error_out = the last e (evaluated once at the end if no chunk ran); either pointer may be NULL.
+ * target > 0 and finite, floor >= 0 and finite, check_every >= 1, 0 <= min_passes <= max_passes, max_passes >= 1. */
+int cl2_run_until(cl2_renderer* r, double target, double floor, int min_passes, int max_passes, int check_every, int* passes_done,
+                  double* error_out);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,21 @@ def per_launch(pattern):
     return {k: {c: (v / n, n) for c, (n, v) in cs.items()} for k, cs in agg.items()}
 
 
+def write_summary(out, path):
+    """The summary as JSON with one line per top-level field and per kernel (a kernel's counters on one line): the same data as
+    an indented dump in a twentieth of the lines."""
+    lines = []
+    for k in sorted(out):
+        v = out[k]
+        if k == "kernels":
+            rows = [f"  {json.dumps(n)}: {json.dumps(v[n], sort_keys=True)}" for n in sorted(v)]
+            lines.append(f" {json.dumps(k)}: {{\n" + ",\n".join(rows) + "\n }")
+        else:
+            lines.append(f" {json.dumps(k)}: {json.dumps(v, sort_keys=True)}")
+    with open(path, "w") as f:
+        f.write("{\n" + ",\n".join(lines) + "\n}\n")
+
+
 def main():
     tag, scene = sys.argv[1], sys.argv[2]
     W, H = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (1920, 1080)
@@ -111,7 +126,7 @@ def main():
                    "MI355X_MICROARCH.md HBM section); SQ_WAVE_CYCLES/SQ_WAIT_*/SQ_ACTIVE_INST_* are quad-cycles",
            "scene": scene, "width": W, "height": H, "sample_streams": streams, "sources_sha": bench.kernel_sources_sha(),
            "conn_traversal_kernel": conn[0] if conn else None, "kernel_trace_timed_region": timed, "kernels": kernels}
-    json.dump(out, open(f"profiles/{tag}_pmc_{scene}{suffix}.json", "w"), indent=1, sort_keys=True)
+    write_summary(out, f"profiles/{tag}_pmc_{scene}{suffix}.json")
     if stats:
         for r in csv.DictReader(open(f"profiles/{tag}_kernel_stats_{scene}{suffix}.csv")):
             if float(r["Percentage"]) > 1:
