@@ -17,7 +17,7 @@
 // [0, n_lds_nodes) and, when they fit, all intersection triangles are copied into LDS by each
 // workgroup (the whole Cornell box: 5 nodes + 16 triangles).
 //
-// Device layouts (built by cl2_upload_scene):
+// Device layouts (built by scene_prep.hpp):
 //   node : float4 lo = {min.xyz, as_float(skip)}, float4 hi = {max.xyz, as_float(info)}      (32 B)
 //          info < 0: inner node.  info >= 0: leaf over triangles [info >> 4, (info >> 4) + (info & 15) + 1).
 //          A reference leaf with more than 16 triangles (only possible past the builder's depth
@@ -27,6 +27,7 @@
 #pragma once
 #include "vecmath.hpp"
 #include "bsdf.hpp"
+#include "scene_layout.hpp"
 
 namespace cl2 {
 
@@ -38,15 +39,11 @@ struct BvhView {
     int n_lds_nodes;         // records staged in LDS (<= LDS_NODE_CAP)
     int lds_tris;            // 1: all triangles staged in LDS (n_tris <= LDS_TRI_CAP)
     int n_fast_nodes;        // records of the pruned table (0: none); only for trees that are wholly staged
-    const float4* fast_nodes;   // the tree without the inner records whose test is not worth its cost (cl2_upload_scene):
+    const float4* fast_nodes;   // the tree without the inner records whose test is not worth its cost (scene_prep.hpp):
                                 // same hits for rays with finite 1/d, fewer box tests
     int fast_flat;              // 1: the pruned table is a plain list of leaves (every record a leaf, skip = index + 1): every lane
                                 // visits the same records in the same order, so the walk's control flow is wave-uniform
 };
-
-constexpr int LDS_NODE_CAP = 512;   // records in the LDS window: at most 512 * 32 B = 16 KB
-constexpr int LDS_TRI_CAP = 512;    // triangles staged in LDS when the whole scene has no more: at most 512 * 48 B = 24 KB
-constexpr int LEAF_PACK_MAX = 16;   // triangles per leaf record
 
 // The staged part of the tree lives in DYNAMIC shared memory sized by the scene (bvh_lds_bytes on the
 // host): the Cornell box takes 1 KB, a 500-triangle scene 40 KB -- one kernel serves both without the
@@ -177,7 +174,7 @@ __device__ __forceinline__ void tri_test_branchless(V3 o, V3 d, const float4& p0
 // tri_test_branchless for the nearest-first walk (bvh_wide.hpp, ORDER): the reference keeps the FIRST triangle it meets at a given t
 // (`t < best_t`, trace.metal:170).  A walk that meets the leaves in another order gets the same winner by letting a hit at exactly
 // best_t replace a held triangle that the reference would have met later (rank[]: position in the reference's visit order, built by
-// cl2_upload_scene; rank[-1] = INT_MIN for "nothing held" -- t = best_t = +inf, a degenerate triangle -- and one entry behind the
+// scene_prep.hpp; rank[-1] = INT_MIN for "nothing held" -- t = best_t = +inf, a degenerate triangle -- and one entry behind the
 // last triangle).  Ties are a few rays in 1e8: the walk tests a pair with tri_test_branchless_tie and comes here, inside a wave-level
 // branch, only when one of the two tied -- repeating a test is harmless (a triangle that holds best_t has no lower rank than itself),
 // and so is the rule where the order IS the reference's (the rays of the binary walk inside the same loop): what is held then has

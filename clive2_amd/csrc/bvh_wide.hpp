@@ -4,7 +4,7 @@
 // Why it is exact.  The reference pops a box, tests it (`tmin <= tmax && tmin < best_t`, tmin/tmax from the slab test),
 // and either pushes its two children (the one at left+1 is popped first) or tests the leaf's triangles in order.  A box
 // nests its children exactly: bounds are min/max over nested triangle sets, rounded float64 -> float32 monotonically
-// (cl2_upload_scene verifies it box by box and disables this walk otherwise).  For a ray with finite 1/d every slab
+// (scene_prep.hpp verifies it box by box and disables this walk otherwise).  For a ray with finite 1/d every slab
 // value is a monotonic function of the bound it comes from, so a child's tmin is >= and its tmax <= its parent's, and
 // best_t only ever shrinks.  Hence: if a box passes its test at the time it is popped, every ancestor passed its own
 // test earlier; if an inner box fails, every box below it fails too.  The inner tests therefore decide nothing that
@@ -25,10 +25,10 @@
 // in a per-lane global array (rare: the dynamic depth of a 4-wide walk is mostly 2..6).
 #pragma once
 #include "bvh_traverse.hpp"
+#include "scene_layout.hpp"
 
 namespace cl2 {
 
-constexpr int WIDE_EMPTY = (int)0x80000000;
 #ifndef CL2_WIDE_STACK_LDS
 #define CL2_WIDE_STACK_LDS 8
 #endif
@@ -44,7 +44,10 @@ constexpr int WIDE_STACK_LDS = CL2_WIDE_STACK_LDS;
 // (Two node visits per pass, by the same reasoning, do NOT pay: 3.80 -> 4.12 ms; nor does a second triangle round in the
 // binary walks, whose pass already tests the first triangles of a leaf together with the node visit that enters it:
 // whole-subpath launch 5.87 -> 6.30 ms on the glass scene, connection launch of the 1M-triangle scene 15.8 -> 16.3 ms.)
-constexpr int WIDE_STACK_OVERFLOW = 136;      // 2 x the reference's 64-entry stack bound + slack: cannot be exceeded (Q18 check at upload)
+// 2 x the reference's 64-entry stack bound + slack: the walk in the reference's child order cannot exceed it (Q18 check at upload).
+// The nearest-first walk (ORDER) pushes siblings in another order, and its depth is not bounded by the pending depth the
+// overflow sizing rests on.
+constexpr int WIDE_STACK_OVERFLOW = 136;
 
 #ifdef CL2_WALK_HISTO
 // instrumentation build only (tools/exp_walk_histo.py): per pass of the wide walk, how many lanes visit a node / test triangles
@@ -72,7 +75,7 @@ struct WideView {
 // instructions per pass, at the one-per-two ratio where the CU's single scalar unit binds, tools/issue_mix.hip); LDS addresses were
 // computed with a multiply by blockDim.x; SGPRs spilled into VGPR lanes.  Here:
 //   * a node visit is 7 x 16-byte global loads issued together, four unconditional slab tests (an empty slot holds a box at
-//     +inf, which can never pass `tmin <= tmax && tmin < best_t`: cl2_upload_scene) and three UNCONDITIONAL 8-byte LDS writes
+//     +inf, which can never pass `tmin <= tmax && tmin < best_t`: scene_prep.hpp) and three UNCONDITIONAL 8-byte LDS writes
 //     of the candidate found so far with `sp += pushed` -- no exec-mask region at all.  Lanes within three entries of the LDS
 //     part's end take the conditional form with the global overflow array (rare, wave-level branch);
 //   * the stack is int2 {ref, tmin} per entry ([entry][thread], one ds_read_b64 / ds_write_b64), 8 entries in LDS, addressed

@@ -18,15 +18,11 @@
 #pragma once
 #include "vecmath.hpp"
 #include "bsdf.hpp"
+#include "scene_layout.hpp"
 
 namespace cl2 {
 
-// The triangles of the camera quad (is_camera, scene.py): the t = 1 pairs ask whether the triangle their ray hit is one of
-// them.  As a look-up in the shading records (tri_shade[4 i + 2].w) that was a dependent load -- a memory round trip of its
-// own -- inside each of the six t = 1 pairs; the reference's scenes have two such triangles, which travel as kernel arguments.
-// More than CAM_TRI_ARGS of them: n < 0 and the look-up stays.
-constexpr int CAM_TRI_ARGS = 4;
-struct CamTris { int n; int idx[CAM_TRI_ARGS]; };
+// Is triangle i one of the camera quad's (CamTris, scene_layout.hpp)?
 __device__ __forceinline__ bool is_camera_tri(const CamTris& ct, const float4* __restrict__ tri_shade, int i) {
     if (ct.n < 0) return __float_as_int(tri_shade[4 * i + 2].w) != 0;
     bool hit = false;

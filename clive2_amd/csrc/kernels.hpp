@@ -44,6 +44,7 @@
 #include "bsdf.hpp"
 #include "bvh_traverse.hpp"
 #include "bvh_wide.hpp"
+#include "scene_layout.hpp"
 
 namespace cl2 {
 
@@ -52,19 +53,8 @@ constexpr int WAVES_PER_BLOCK = BLOCK / 64;
 constexpr int MAX_VERTS = 6;          // bounce loop bound, trace.metal:407
 constexpr int CONN_SLOTS = 36;        // (t in 1..6) x (s in 1..6) strategy pairs that need a ray
 constexpr int TAG_PID_BITS = 26;
-constexpr int SHADE_LDS_CAP = 128;   // shading triangles staged in LDS by the subpath kernel (64 B each)
-constexpr int LDS_MAT_CAP = 32;      // materials staged in LDS by the subpath kernel
 constexpr int META_HIT_LIGHT = 1 << 8;
 constexpr int META_HIT_CAMERA = 1 << 9;
-
-struct CameraRec {   // byte-identical to struct Camera, trace.metal:72-85
-    float center[4], focal_point[4], direction[4], dx[4], dy[4];
-    int pixel_width, pixel_height;
-    float phys_width, phys_height, h_fov, v_fov;
-    int pad[2];
-};
-
-struct MaterialDev { float4 color_type; float4 emission_alpha; float ior; float pad[3]; };  // 48 B
 
 struct PathBufs {
     float4 *P0, *P1, *P2, *P3;
@@ -360,11 +350,8 @@ __global__ __launch_bounds__(BLOCK, TALLY ? 6 : 8) __attribute__((amdgpu_num_sgp
 // one level per launch when paths die quickly (open scenes, glass).
 //
 // Vertices `first` (written by the generator or the previous launch) is patched in place; the vertex
-// created at level end-1 is written complete (reverse pdf still open) when the path goes on.
-struct ShadeLds {
-    float4 tri_shade[4 * SHADE_LDS_CAP];
-    MaterialDev mats[LDS_MAT_CAP];
-};
+// created at level end-1 is written complete (reverse pdf still open) when the path goes on.  Small scenes stage their shading
+// records and materials in LDS (ShadeLds, scene_layout.hpp).
 
 // Where the shading records of a launch live: LDS copies for small scenes, else global memory.
 struct ShadeSrc {

@@ -26,18 +26,13 @@
 #include "bvh_builder.hpp"
 #include "comm_rccl.hpp"
 #include "comm_wait.hpp"
+#include "scene_prep.hpp"
 
 using namespace cl2;
 
 namespace {
 
 thread_local std::string g_create_error;
-
-// Reference AoS records as the host hands them over (src/struct_types.py).
-struct BoxRec { float min[4], max[4]; int32_t left, right, pad[2]; };
-struct TriRec { float v0[4], v1[4], v2[4], n0[4], n1[4], n2[4], normal[4]; int32_t material, is_light, is_camera, pad; };
-struct MatRec { float color[4], emission[4]; int32_t type; float alpha, ior; int32_t pad; };
-static_assert(sizeof(BoxRec) == 48 && sizeof(TriRec) == 128 && sizeof(MatRec) == 48 && sizeof(CameraRec) == 112, "ABI");
 
 enum Stage { ST_GENERATE, ST_TRAVERSE_PATHS, ST_BOUNCE, ST_CONNECT_SETUP, ST_TRAVERSE_CONN, ST_CONNECT_RESOLVE,
              ST_FINALIZE, ST_ACCUMULATE, ST_COUNT };
@@ -92,7 +87,7 @@ struct cl2_renderer {
     int n_fast = 0;                      // records of the pruned table (bvh.n_fast_nodes unless debug_flags bit 7 switches it off)
     CamTris cam_tris{0, {0, 0, 0, 0}};   // the triangles with is_camera set, as kernel arguments of the resolve stage (n < 0: too many, look them up)
     int fast_flat = 0;                   // the pruned table is a plain list of leaves (bvh.fast_flat unless debug_flags bit 11 switches it off)
-    float4* d_fast = nullptr;            // pruned record table of an LDS-resident tree (cl2_upload_scene); bvh.n_fast_nodes == 0: none
+    float4* d_fast = nullptr;            // pruned record table of an LDS-resident tree (scene_prep.hpp); bvh.n_fast_nodes == 0: none
     WideView wide{};
     int2* d_wide_ovf = nullptr;          // per-lane stack overflow of the wide launches (one region per stage: [2]); allocated by the first wide launch
     int wide_ovf_entries = 0;            // entries per lane: the deepest stack this tree can produce (cl2_upload_scene)
@@ -192,8 +187,14 @@ template <typename T> void dev_free(cl2_renderer* r, T*& p) {
     p = nullptr;
 }
 
+// device copy of n host elements (a scene array)
+template <typename T> int upload(cl2_renderer* r, T** p, const T* h, size_t n) {
+    TRY(dev_alloc(r, p, n));
+    HIP_TRY(r, hipMemcpy(*p, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return CL2_OK;
+}
+
 int fail(cl2_renderer* r, int code, const std::string& msg) { r->err = msg; return code; }
-inline float as_f_int(int32_t i) { float f; std::memcpy(&f, &i, 4); return f; }
 
 inline int grid_for(size_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
 
@@ -904,362 +905,55 @@ int cl2_upload_scene(cl2_renderer* r, const void* boxes_v, int n_boxes, const vo
                      const int32_t* light_tri_index, int light_count) {
     if (!r) return CL2_E_INVALID;
     r->features_valid = false;           // the features describe the scene they were rendered from
-    if (!boxes_v || !tris_v || !mats_v || !camera_v || !light_tris_v || !light_areas || !light_tri_index)
-        return fail(r, CL2_E_INVALID, "NULL scene array");
-    if (n_boxes < 1 || n_tris < 1 || light_count < 1) return fail(r, CL2_E_INVALID, "scene needs >=1 box, triangle and light");
-    if (n_tris >= (1 << 27)) return fail(r, CL2_E_INVALID, "at most 2^27 triangles (leaf records pack begin<<4 | count-1)");
-    // material 7 is hard-wired into the camera vertices (trace.metal:611, :1053); at most 256 fit the packed meta word
-    if (n_mats < 8 || n_mats > 256) return fail(r, CL2_E_INVALID, "material table must have 8..256 entries");
-    const BoxRec* boxes = static_cast<const BoxRec*>(boxes_v);
-    const TriRec* tris = static_cast<const TriRec*>(tris_v);
-    const MatRec* mats = static_cast<const MatRec*>(mats_v);
-    const TriRec* ltris = static_cast<const TriRec*>(light_tris_v);
-    CameraRec cam;
-    std::memcpy(&cam, camera_v, sizeof cam);
-    if (cam.pixel_width != r->W || cam.pixel_height != r->H)
-        return fail(r, CL2_E_INVALID, "camera resolution differs from the renderer's");
-
-    // ---- validate the tree: every index in range, children after their parent (breadth-first
-    // numbering, src/bvh.py:345-351) and every box reached exactly once -- which also guarantees
-    // that the stackless walk terminates ----
-    std::vector<char> reached(n_boxes, 0);
-    reached[0] = 1;
-    for (int i = 0; i < n_boxes; i++) {
-        const BoxRec& b = boxes[i];
-        if (!reached[i]) return fail(r, CL2_E_INVALID, "box " + std::to_string(i) + " is not reachable from the root");
-        if (b.right == 0) {
-            if (b.left <= i || b.left + 1 >= n_boxes) return fail(r, CL2_E_INVALID, "inner box child index out of order/range");
-            if (reached[b.left] || reached[b.left + 1]) return fail(r, CL2_E_INVALID, "box has two parents");
-            reached[b.left] = reached[b.left + 1] = 1;
-        } else {
-            if (b.left < 0 || b.right > n_tris || b.left >= b.right) return fail(r, CL2_E_INVALID, "leaf triangle range out of range");
-        }
-    }
-    // ---- visit order (node, right subtree, left subtree = the reference's pop order, trace.metal:150-160)
-    // and subtree sizes in records; leaves with more than LEAF_PACK_MAX triangles take extra records ----
-    auto leaf_records = [&](const BoxRec& b) { return (b.right - b.left + LEAF_PACK_MAX - 1) / LEAF_PACK_MAX; };
-    std::vector<int> subtree(n_boxes, 0);
-    for (int i = n_boxes - 1; i >= 0; i--) {            // children have larger indices than their parent
-        const BoxRec& b = boxes[i];
-        subtree[i] = b.right == 0 ? 1 + subtree[b.left] + subtree[b.left + 1] : leaf_records(b);
-    }
-    const int n_records = subtree[0];
-    std::vector<int> rec_index(n_boxes, -1);
-    // `pending[i]`: entries on the reference's stack underneath box i when it is popped.  The reference's loop
-    // runs `while (stack_ptr > 0 && stack_ptr < 64)` (trace.metal:149): a walk that enters an inner box with 62
-    // entries pending pushes to 64 and ENDS there, whatever is still unvisited (quirk Q18).  The stackless walk has
-    // no such limit, so a tree that could reach it is refused instead of being rendered differently; the
-    // reference's builder stops splitting at 32 pending boxes (bvh.py:294, Q13), far below.
-    std::vector<int> pending(n_boxes, 0);
-    rec_index[0] = 0;
-    for (int i = 0; i < n_boxes; i++) {                  // parents before children: their record index is known
-        const BoxRec& b = boxes[i];
-        if (b.right == 0) {
-            if (pending[i] + 2 >= 64)
-                return fail(r, CL2_E_INVALID, "tree too deep: the reference's 64-entry traversal stack would overflow at box " + std::to_string(i));
-            rec_index[b.left + 1] = rec_index[i] + 1;                            // right child: adjacent
-            rec_index[b.left] = rec_index[i] + 1 + subtree[b.left + 1];          // left child: after the right subtree
-            pending[b.left + 1] = pending[i] + 1;                                // popped first, its sibling waits below it
-            pending[b.left] = pending[i];
-        }
-    }
-    // ---- record numbering.  Small trees: plain visit order.  Trees larger than the LDS window: the
-    // boxes of the TOP levels (the reference array is breadth-first, so a prefix of it) are numbered
-    // first, [0, n_top), so that the window staged in LDS holds the records every ray visits; the rest
-    // keep their visit order behind them.  Links are explicit (skip, and the right child in `info`),
-    // so the numbering has no influence on the walk. ----
-    int n_top = 0;
-    if (n_records > LDS_NODE_CAP) {
-        while (n_top < n_boxes && n_top < LDS_NODE_CAP && (boxes[n_top].right == 0 || leaf_records(boxes[n_top]) == 1)) n_top++;
-    }
-    std::vector<int> renum((size_t)n_records + 1);
-    {
-        std::vector<char> is_top((size_t)n_records, 0);
-        for (int i = 0; i < n_top; i++) is_top[rec_index[i]] = 1;
-        int tops_before = 0;
-        for (int k = 0; k < n_records; k++) {
-            if (is_top[k]) { tops_before++; continue; }
-            renum[k] = n_top + k - tops_before;
-        }
-        for (int i = 0; i < n_top; i++) renum[rec_index[i]] = i;
-        renum[n_records] = n_records;
-    }
-    for (int t = 0; t < n_tris; t++) {
-        if (tris[t].material < 0 || tris[t].material >= n_mats) return fail(r, CL2_E_INVALID, "triangle material index out of range");
-    }
-    for (int l = 0; l < light_count; l++) {
-        if (light_tri_index[l] < 0 || light_tri_index[l] >= n_tris) return fail(r, CL2_E_INVALID, "light triangle index out of range");
-        if (ltris[l].material < 0 || ltris[l].material >= n_mats) return fail(r, CL2_E_INVALID, "light material index out of range");
-    }
-
-    // ---- 4-wide collapse for the exact wide walk (bvh_wide.hpp).  Conditions: the root is an inner box, every box
-    // nests its children exactly (what the exactness argument rests on; true for trees that np_flatten_bvh or either
-    // native builder made, not guaranteed for hand-made Box[] arrays) and no leaf exceeds one record. ----
-    std::vector<float4> h_wide;
-    int n_wide = 0;
-    bool nests = false;
-    {
-        bool ok = n_boxes >= 3 && boxes[0].right == 0;
-        auto inside = [&](const BoxRec& c, const BoxRec& p) {
-            for (int k = 0; k < 3; k++) if (!(c.min[k] >= p.min[k] && c.max[k] <= p.max[k])) return false;
-            return true;
-        };
-        for (int i = 0; i < n_boxes && ok; i++) {
-            const BoxRec& b = boxes[i];
-            if (b.right == 0) ok = inside(boxes[b.left], b) && inside(boxes[b.left + 1], b);
-            else ok = (b.right - b.left) <= LEAF_PACK_MAX;
-        }
-        nests = ok;
-        if (ok) {
-            // slots of reference box x in its visit order: child left+1 first, each inner child replaced by its children
-            auto slots_of = [&](int x, int* out) {
-                int n = 0;
-                for (int c : {boxes[x].left + 1, boxes[x].left}) {
-                    if (boxes[c].right != 0) out[n++] = c;
-                    else { out[n++] = boxes[c].left + 1; out[n++] = boxes[c].left; }
-                }
-                return n;
-            };
-            std::vector<int> wide_of(n_boxes, -1), order;
-            order.push_back(0); wide_of[0] = 0;
-            for (size_t h = 0; h < order.size(); h++) {
-                int sl[4];
-                const int n = slots_of(order[h], sl);
-                for (int k = 0; k < n; k++)
-                    if (boxes[sl[k]].right == 0) { wide_of[sl[k]] = (int)order.size(); order.push_back(sl[k]); }
-            }
-            n_wide = (int)order.size();
-            h_wide.assign((size_t)8 * n_wide, make_float4(0, 0, 0, 0));
-            for (int wn = 0; wn < n_wide; wn++) {
-                int sl[4];
-                const int n = slots_of(order[wn], sl);
-                float v[6][4];
-                int ref[4];
-                for (int k = 0; k < 4; k++) {
-                    ref[k] = WIDE_EMPTY;
-                    // an empty slot holds a box at +inf: for a ray with finite 1/d its slab test gives tmin = +inf or tmax = -inf,
-                    // so `tmin <= tmax && tmin < best_t` fails without the walk looking at the reference (bvh_wide.hpp)
-                    for (int c = 0; c < 6; c++) v[c][k] = std::numeric_limits<float>::infinity();
-                    if (k >= n) continue;
-                    const BoxRec& b = boxes[sl[k]];
-                    for (int c = 0; c < 3; c++) { v[c][k] = b.min[c]; v[3 + c][k] = b.max[c]; }
-                    ref[k] = b.right == 0 ? wide_of[sl[k]] : ~((b.left << 4) | (b.right - b.left - 1));
-                }
-                for (int c = 0; c < 6; c++) h_wide[(size_t)8 * wn + c] = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
-                h_wide[(size_t)8 * wn + 6] = make_float4(as_f_int(ref[0]), as_f_int(ref[1]), as_f_int(ref[2]), as_f_int(ref[3]));
-            }
-        }
-    }
-
-    // ---- repack ----
-    std::vector<float4> h_nodes(2 * (size_t)n_records), h_tris(3 * (size_t)n_tris), h_shade(4 * (size_t)n_tris),
-        h_ltris(5 * (size_t)light_count);
-    auto as_f = [](int32_t i) { float f; std::memcpy(&f, &i, 4); return f; };
-    const float inf = std::numeric_limits<float>::infinity();
-    for (int i = 0; i < n_boxes; i++) {
-        const BoxRec& b = boxes[i];
-        const int k = rec_index[i], skip = renum[k + subtree[i]];
-        if (b.right == 0) {
-            // inner: info = ~(record of the right child, visited first), negative
-            h_nodes[2 * (size_t)renum[k]] = make_float4(b.min[0], b.min[1], b.min[2], as_f(skip));
-            h_nodes[2 * (size_t)renum[k] + 1] = make_float4(b.max[0], b.max[1], b.max[2], as_f(~renum[k + 1]));
-        } else {
-            int begin = b.left;
-            for (int part = 0; begin < b.right; part++, begin += LEAF_PACK_MAX) {
-                const int count = std::min(LEAF_PACK_MAX, b.right - begin);
-                const int info = (begin << 4) | (count - 1);
-                // follow-up records of an oversized leaf: an unbounded box, so they are always entered
-                const int nxt = renum[k + part + 1];
-                const float4 lo = part == 0 ? make_float4(b.min[0], b.min[1], b.min[2], as_f(nxt))
-                                            : make_float4(-inf, -inf, -inf, as_f(nxt));
-                const float4 hi = part == 0 ? make_float4(b.max[0], b.max[1], b.max[2], as_f(info))
-                                            : make_float4(inf, inf, inf, as_f(info));
-                h_nodes[2 * (size_t)renum[k + part]] = lo;
-                h_nodes[2 * (size_t)renum[k + part] + 1] = hi;
-            }
-        }
-    }
-    // ---- pruned table for the LDS-resident walk.  For a ray with finite 1/d an inner box's test can only prune (same
-    // argument as the wide walk: a child that passes its test implies its parent passed), so an inner record may be
-    // dropped and its children visited unconditionally without changing any hit.  A record is dropped when the test is
-    // expected to cost more than it saves: (1 - area / area of the nearest tested ancestor) x cost of the subtree < 1
-    // box test, the surface-area estimate of the chance that a ray that reached the ancestor misses this box.  The
-    // Cornell box loses its root and its one other inner box (both span the room): 3 box tests per ray instead of 5.
-    // Rays with a non-finite 1/d, and the counting mode, walk the full table. ----
-    std::vector<float4> h_fast;
-    int n_fast = 0;
-    if (nests && n_top == 0 && n_records <= LDS_NODE_CAP && n_tris <= LDS_TRI_CAP) {
-        auto area = [&](const BoxRec& b) {
-            const double x = (double)b.max[0] - b.min[0], y = (double)b.max[1] - b.min[1], z = (double)b.max[2] - b.min[2];
-            return 2.0 * (x * y + y * z + z * x);
-        };
-        std::vector<double> cost(n_boxes, 0.0), anc_area(n_boxes, 0.0);
-        for (int i = n_boxes - 1; i >= 0; i--) {
-            const BoxRec& b = boxes[i];
-            cost[i] = b.right == 0 ? 1.0 + cost[b.left] + cost[b.left + 1] : 1.0 + 2.5 * (b.right - b.left);
-        }
-        std::vector<char> dropped((size_t)n_records + 1, 0);
-        anc_area[0] = area(boxes[0]);
-        for (int i = 0; i < n_boxes; i++) {
-            const BoxRec& b = boxes[i];
-            if (b.right != 0) continue;
-            const double a = area(b);
-            const double p_miss = anc_area[i] > 0.0 ? std::max(0.0, 1.0 - a / anc_area[i]) : 0.0;
-            const bool drop = p_miss * (cost[i] - 1.0) < 1.0;
-            dropped[rec_index[i]] = drop ? 1 : 0;
-            anc_area[b.left] = anc_area[b.left + 1] = drop ? anc_area[i] : a;
-        }
-        std::vector<int> fast_index((size_t)n_records + 1);
-        for (int k = 0; k <= n_records; k++) { fast_index[k] = n_fast; if (k < n_records && !dropped[k]) n_fast++; }
-        // LDS budget: the pruned table sits beside the full one (rays with a non-finite 1/d need that) in every workgroup
-        // that stages the tree.  Three such workgroups per CU (160 KB) is what the subpath kernel runs at with its 9.7 KB
-        // of static shading tables; a scene near the 512-record / 512-triangle caps would lose a workgroup per CU to the
-        // extra table (and a 64-KB-per-workgroup part would refuse the launch), so there it is not built.
-        const size_t lds_with_fast = ((size_t)2 * n_records + (size_t)3 * n_tris + (size_t)2 * n_fast) * sizeof(float4) + sizeof(ShadeLds);
-        if (n_fast < n_records && lds_with_fast > (size_t)160 * 1024 / 3) n_fast = n_records;       // -> no table
-        if (n_fast < n_records) {
-            h_fast.resize(2 * (size_t)n_fast);
-            for (int i = 0; i < n_boxes; i++) {
-                const int k = rec_index[i];
-                if (dropped[k]) continue;
-                float4 lo = h_nodes[2 * (size_t)k], hi = h_nodes[2 * (size_t)k + 1];
-                lo.w = as_f(fast_index[k + subtree[i]]);
-                if (boxes[i].right == 0) hi.w = as_f(~fast_index[k + 1]);
-                h_fast[2 * (size_t)fast_index[k]] = lo;
-                h_fast[2 * (size_t)fast_index[k] + 1] = hi;
-            }
-        } else {
-            n_fast = 0;
-        }
-    }
-
-    CamTris cam_tris{0, {0, 0, 0, 0}};
-    for (int t = 0; t < n_tris; t++) {
-        if (!tris[t].is_camera || cam_tris.n < 0) continue;
-        if (cam_tris.n == CAM_TRI_ARGS) cam_tris.n = -1;
-        else cam_tris.idx[cam_tris.n++] = t;
-    }
-    for (int t = 0; t < n_tris; t++) {
-        const TriRec& T = tris[t];
-        // edge vectors: the same binary32 subtractions ray_triangle_intersect performs (trace.metal:118-119)
-        h_tris[3 * t] = make_float4(T.v0[0], T.v0[1], T.v0[2], 0.0f);
-        h_tris[3 * t + 1] = make_float4(T.v1[0] - T.v0[0], T.v1[1] - T.v0[1], T.v1[2] - T.v0[2], 0.0f);
-        h_tris[3 * t + 2] = make_float4(T.v2[0] - T.v0[0], T.v2[1] - T.v0[1], T.v2[2] - T.v0[2], 0.0f);
-        h_shade[4 * t] = make_float4(T.n0[0], T.n0[1], T.n0[2], as_f(T.material));
-        h_shade[4 * t + 1] = make_float4(T.n1[0], T.n1[1], T.n1[2], as_f(T.is_light ? 1 : 0));
-        h_shade[4 * t + 2] = make_float4(T.n2[0], T.n2[1], T.n2[2], as_f(T.is_camera ? 1 : 0));
-        h_shade[4 * t + 3] = make_float4(T.normal[0], T.normal[1], T.normal[2], 0.0f);
-    }
-    for (int l = 0; l < light_count; l++) {
-        const TriRec& T = ltris[l];
-        h_ltris[5 * l] = make_float4(T.v0[0], T.v0[1], T.v0[2], 0.0f);
-        h_ltris[5 * l + 1] = make_float4(T.v1[0], T.v1[1], T.v1[2], 0.0f);
-        h_ltris[5 * l + 2] = make_float4(T.v2[0], T.v2[1], T.v2[2], 0.0f);
-        h_ltris[5 * l + 3] = make_float4(T.normal[0], T.normal[1], T.normal[2], 0.0f);
-        h_ltris[5 * l + 4] = make_float4(as_f(T.material), 0.0f, 0.0f, 0.0f);
-    }
-    std::vector<MaterialDev> h_mats(n_mats);
-    for (int m = 0; m < n_mats; m++) {
-        h_mats[m].color_type = make_float4(mats[m].color[0], mats[m].color[1], mats[m].color[2], as_f(mats[m].type));
-        h_mats[m].emission_alpha = make_float4(mats[m].emission[0], mats[m].emission[1], mats[m].emission[2], mats[m].alpha);
-        h_mats[m].ior = mats[m].ior;
-        h_mats[m].pad[0] = h_mats[m].pad[1] = h_mats[m].pad[2] = 0.0f;
-    }
+    PreparedScene p;
+    const std::string msg = prepare_scene(boxes_v, n_boxes, tris_v, n_tris, mats_v, n_mats, camera_v, light_tris_v, light_areas,
+                                          light_tri_index, light_count, r->W, r->H, p);
+    if (!msg.empty()) return fail(r, CL2_E_INVALID, msg);
 
     HIP_TRY(r, hipSetDevice(r->device));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     r->scene_ok = false;
     dev_free(r, r->d_nodes); dev_free(r, r->d_tris); dev_free(r, r->d_tri_shade);
     dev_free(r, r->d_mats); dev_free(r, r->d_light_tris); dev_free(r, r->d_light_areas); dev_free(r, r->d_light_tri_index);
-    TRY(dev_alloc(r, &r->d_nodes, h_nodes.size()));
-    TRY(dev_alloc(r, &r->d_tris, h_tris.size()));
-    TRY(dev_alloc(r, &r->d_tri_shade, h_shade.size()));
-    TRY(dev_alloc(r, &r->d_mats, h_mats.size()));
-    TRY(dev_alloc(r, &r->d_light_tris, h_ltris.size()));
-    TRY(dev_alloc(r, &r->d_light_areas, (size_t)light_count));
-    TRY(dev_alloc(r, &r->d_light_tri_index, (size_t)light_count));
-    HIP_TRY(r, hipMemcpy(r->d_nodes, h_nodes.data(), h_nodes.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_TRY(r, hipMemcpy(r->d_tris, h_tris.data(), h_tris.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_TRY(r, hipMemcpy(r->d_tri_shade, h_shade.data(), h_shade.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_TRY(r, hipMemcpy(r->d_mats, h_mats.data(), h_mats.size() * sizeof(MaterialDev), hipMemcpyHostToDevice));
-    HIP_TRY(r, hipMemcpy(r->d_light_tris, h_ltris.data(), h_ltris.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_TRY(r, hipMemcpy(r->d_light_areas, light_areas, (size_t)light_count * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(r, hipMemcpy(r->d_light_tri_index, light_tri_index, (size_t)light_count * sizeof(int), hipMemcpyHostToDevice));
-
-    dev_free(r, r->d_wide);
-    dev_free(r, r->d_tris36);
-    r->wide.tris36 = nullptr;
-    dev_free(r, r->d_tri_rank);
-    r->wide.tri_rank = nullptr;
+    dev_free(r, r->d_wide); dev_free(r, r->d_tris36); dev_free(r, r->d_tri_rank); dev_free(r, r->d_fast);
+    r->wide.tris36 = nullptr; r->wide.tri_rank = nullptr;
+    r->bvh.fast_nodes = nullptr; r->bvh.n_fast_nodes = 0;
     r->n_wide = 0;
-    if (n_wide > 0) {
-        // the wide walk reads the triangle records without their three padding words (36 bytes each; bvh_wide.hpp, PACK)
-        {
-            std::vector<float> h36((size_t)9 * n_tris + 9, 0.0f);          // + one record of padding: the pair load of the last triangle reads it
-            for (int t = 0; t < n_tris; t++)
-                for (int v = 0; v < 3; v++) {
-                    const float4 q = h_tris[3 * (size_t)t + v];
-                    h36[9 * (size_t)t + 3 * v] = q.x; h36[9 * (size_t)t + 3 * v + 1] = q.y; h36[9 * (size_t)t + 3 * v + 2] = q.z;
-                }
-            TRY(dev_alloc(r, &r->d_tris36, h36.size()));
-            HIP_TRY(r, hipMemcpy(r->d_tris36, h36.data(), h36.size() * sizeof(float), hipMemcpyHostToDevice));
-            r->wide.tris36 = r->d_tris36;
-        }
-        TRY(dev_alloc(r, &r->d_wide, h_wide.size()));
-        HIP_TRY(r, hipMemcpy(r->d_wide, h_wide.data(), h_wide.size() * sizeof(float4), hipMemcpyHostToDevice));
+    TRY(upload(r, &r->d_nodes, p.nodes.data(), p.nodes.size()));
+    TRY(upload(r, &r->d_tris, p.tris.data(), p.tris.size()));
+    TRY(upload(r, &r->d_tri_shade, p.shade.data(), p.shade.size()));
+    TRY(upload(r, &r->d_mats, p.mats.data(), p.mats.size()));
+    TRY(upload(r, &r->d_light_tris, p.ltris.data(), p.ltris.size()));
+    TRY(upload(r, &r->d_light_areas, light_areas, (size_t)light_count));
+    TRY(upload(r, &r->d_light_tri_index, light_tri_index, (size_t)light_count));
+    if (p.n_wide > 0) {
+        TRY(upload(r, &r->d_tris36, p.tris36.data(), p.tris36.size()));
+        TRY(upload(r, &r->d_wide, p.wide.data(), p.wide.size()));
+        TRY(upload(r, &r->d_tri_rank, p.tri_rank.data(), p.tri_rank.size()));
         // deepest wide stack of THIS tree (see ensure_wide_overflow); a new scene may need a different size
-        int max_pending = 0;
-        for (int i = 0; i < n_boxes; i++) max_pending = std::max(max_pending, pending[i]);
-        const int entries = std::min((int)WIDE_STACK_OVERFLOW, 2 * max_pending + 4);
+        const int entries = std::min((int)WIDE_STACK_OVERFLOW, 2 * p.max_pending + 4);
         if (entries != r->wide_ovf_entries) { dev_free(r, r->d_wide_ovf); r->wide_ovf_entries = entries; }
-        r->wide.nodes = r->d_wide; r->wide.tris = r->d_tris;
-        r->wide.root_lo = make_float4(boxes[0].min[0], boxes[0].min[1], boxes[0].min[2], 0.0f);
-        r->wide.root_hi = make_float4(boxes[0].max[0], boxes[0].max[1], boxes[0].max[2], 0.0f);
-        // The nearest-first walk (ORDER) settles exact-t ties the way the reference does -- the triangle it meets FIRST wins,
-        // trace.metal:170 -- from each triangle's position in the reference's visit order (child left+1 first, a leaf's triangles in
-        // index order).  np_flatten_bvh numbers leaves breadth-first, so the index alone does not say it.  Read on ties only.
-        {
-            // [0]: "nothing held" (best.tri = -1) ranks before everything; [1 + t]: triangle t; [1 + n_tris]: behind the last triangle
-            std::vector<int> h_rank((size_t)n_tris + 2, 0x7fffffff), st{0};
-            h_rank[0] = (int)0x80000000;
-            int next_rank = 0;
-            while (!st.empty()) {
-                const int x = st.back(); st.pop_back();
-                const BoxRec& bx = boxes[x];
-                if (bx.right == 0) { st.push_back(bx.left); st.push_back(bx.left + 1); continue; }   // left+1 on top: popped first
-                for (int t = bx.left; t < bx.right; t++) if (h_rank[1 + (size_t)t] == 0x7fffffff) h_rank[1 + (size_t)t] = next_rank++;
-            }
-            TRY(dev_alloc(r, &r->d_tri_rank, h_rank.size()));
-            HIP_TRY(r, hipMemcpy(r->d_tri_rank, h_rank.data(), h_rank.size() * sizeof(int), hipMemcpyHostToDevice));
-            r->wide.tri_rank = r->d_tri_rank + 1;
-        }
-        r->n_wide = n_wide;
+        const BoxRec& root = static_cast<const BoxRec*>(boxes_v)[0];
+        r->wide.nodes = r->d_wide; r->wide.tris = r->d_tris; r->wide.tris36 = r->d_tris36;
+        r->wide.tri_rank = r->d_tri_rank + 1;   // read on exact-t ties only (ORDER); [-1] ranks "nothing held"
+        r->wide.root_lo = make_float4(root.min[0], root.min[1], root.min[2], 0.0f);
+        r->wide.root_hi = make_float4(root.max[0], root.max[1], root.max[2], 0.0f);
+        r->n_wide = p.n_wide;
     }
     r->bvh.nodes = r->d_nodes; r->bvh.tris = r->d_tris;
-    r->bvh.n_nodes = n_records; r->bvh.n_tris = n_tris;
-    r->bvh.n_lds_nodes = std::min(n_records, LDS_NODE_CAP);
+    r->bvh.n_nodes = p.n_records; r->bvh.n_tris = n_tris;
+    r->bvh.n_lds_nodes = std::min(p.n_records, LDS_NODE_CAP);
     r->bvh.lds_tris = n_tris <= LDS_TRI_CAP ? 1 : 0;
-    dev_free(r, r->d_fast);
-    r->bvh.fast_nodes = nullptr; r->bvh.n_fast_nodes = 0;
-    if (n_fast > 0) {
-        TRY(dev_alloc(r, &r->d_fast, h_fast.size()));
-        HIP_TRY(r, hipMemcpy(r->d_fast, h_fast.data(), h_fast.size() * sizeof(float4), hipMemcpyHostToDevice));
-        r->bvh.fast_nodes = r->d_fast; r->bvh.n_fast_nodes = ((r->debug_flags >> 7) & 1) ? 0 : n_fast;
+    if (p.n_fast > 0) {
+        TRY(upload(r, &r->d_fast, p.fast.data(), p.fast.size()));
+        r->bvh.fast_nodes = r->d_fast; r->bvh.n_fast_nodes = ((r->debug_flags >> 7) & 1) ? 0 : p.n_fast;
     }
-    r->n_fast = n_fast;
-    // a table without inner records, every skip link pointing at the next record: all rays visit the same records in the
-    // same order and the walk's control flow can be wave-uniform (closest_hit_flat)
-    r->fast_flat = n_fast > 0 ? 1 : 0;
-    for (int j = 0; j < n_fast; j++) {
-        int skip, info;
-        std::memcpy(&skip, &h_fast[2 * (size_t)j].w, 4);
-        std::memcpy(&info, &h_fast[2 * (size_t)j + 1].w, 4);
-        if (info < 0 || skip != j + 1) r->fast_flat = 0;
-    }
+    r->n_fast = p.n_fast;
+    r->fast_flat = p.fast_flat;
     r->bvh.fast_flat = ((r->debug_flags >> 11) & 1) ? 0 : r->fast_flat;
-    r->n_mats = n_mats; r->light_count = light_count; r->cam = cam;
-    r->cam_tris = cam_tris;
-    r->n_top = n_top;
+    r->n_mats = n_mats; r->light_count = light_count; r->cam = p.cam;
+    r->cam_tris = p.cam_tris;
+    r->n_top = p.n_top;
     r->scene_ok = true;
     r->paths_share = 0;                  // re-tune the stage shares for the new scene
     r->levels_auto = 0;

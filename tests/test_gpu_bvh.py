@@ -8,6 +8,8 @@ import time
 import numpy as np
 import pytest
 
+from tree_reference import pending_depths
+
 pytestmark = pytest.mark.gpu
 LIGHT, CAMERA = 0, 1
 
@@ -39,10 +41,7 @@ def _check_convention(scene, max_members=8):
     assert np.array_equal(np.minimum(b["min"][li], b["min"][li + 1])[:, :3], b["min"][inner][:, :3])
     assert np.array_equal(np.maximum(b["max"][li], b["max"][li + 1])[:, :3], b["max"][inner][:, :3])
     # the reference's traversal stack: entries pending under each box (left+1 is popped first)
-    pending = np.zeros(nb, np.int64)
-    for i in np.flatnonzero(inner):
-        pending[left[i] + 1] = pending[i] + 1
-        pending[left[i]] = pending[i]
+    pending = pending_depths(b)
     assert pending.max() + 2 <= np.log2(max(nt, 2)) + 3                   # smaller subtree first: O(log n), far below 64
     return pending.max()
 
