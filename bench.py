@@ -8,7 +8,7 @@ buffer); the accumulators are summed once with an in-place RCCL all-reduce (insi
 cl2_reduce_accumulators) inside the timed region.  One "ray" = one closest-hit BVH query
 (SURVEY.md §8d); rays are counted on the device.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080] [--total-spp S] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 1920 --height 1080] [--total-spp S] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,6 +20,12 @@ from its environment.  Default is weak scaling (every rank renders K samples of 
 splits a FIXED S samples over the ranks (strong scaling: configs 4 / 5 of BASELINE.json).  torch is
 not imported (the library runs on the ROCm runtime it was built for; barrier, max-over-ranks clock
 and ray tally go through cl2_comm_allreduce_f64).  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs and no more: scene and renderer, the warm-up (the launch-organisation tuner,
+then W samples in counting mode, which also give N_node / N_tri), the K timed samples, `--dump-outputs`, the line.  Its
+`roofline` holds what the timed region itself measured.  `--full` adds everything that takes runs of its own: the serial
+per-stage breakdown after the clock (`stage_ms`, the `*_alone` launch figures), `serial_run_sample_ms`, the mesh legs, the
+strong-scaling leg of an N > 1 job and `cpu_baseline`.  Nothing before or inside the clock depends on `--full`.
 
 `roofline` describes the dominant kernel (the connection-ray traversal launch, 70 % of all rays):
 its duration is measured live with HIP events on the stream it is launched on.  On the Cornell box
@@ -436,7 +442,7 @@ def _build_scene(name, W, H, builder=None, max_members=None):
 
 
 def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world, with_comm, streams=1, order=0, dump_dir=None):
-    """Warm-up (tuner + counting pass), the timed region, a serial per-stage breakdown.  `steps` = samples THIS
+    """Warm-up (tuner + counting pass), the timed region, with `args.full` a serial per-stage breakdown.  `steps` = samples THIS
     rank renders inside the clock; with `streams` = K sample streams (cl2_set_sample_streams: K independent samples of the
     frame per pass, one seed buffer each) that is ceil(steps / K) passes.  `dump_dir`: rank 0 writes the accumulators the
     timed region left there (dump_outputs), before the breakdown adds to them.  Returns the pieces of the JSON line that depend
@@ -492,7 +498,8 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
     cw = r.counters()
     n_node = cw["box_tests"] / max(cw["counted_rays"], 1)
     n_tri = cw["tri_tests"] / max(cw["counted_rays"], 1)
-    # what the walk that RUNS fetches (the exact 4-wide walk of the scenes whose tree is read through the caches; counting mode 2)
+    # what the walk that RUNS fetches (the exact 4-wide walk of the scenes whose tree is read through the caches; counting mode 2).
+    # A plain run does this too: its samples advance the seed buffers the timed samples start from
     own = None
     if not r.organisation()["tree_in_lds"] and r.organisation()["wide_nodes"] > 0:
         r.reset_counters()
@@ -522,18 +529,20 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
     assert r_org["paths_share"] == org_before["paths_share"], "a tuning experiment ran inside the timed region"
     rays_local = c["rays"]
     dumped = dump_outputs(dump_dir, r) if dump_dir and rank == 0 else None
-    # untimed: per-stage breakdown (HIP events around every launch) over a few more samples, in serial
-    # order on one stream -- with the sample pipeline on, spans of the two streams overlap and a
-    # stage's span includes whatever ran beside it
-    n_break_passes = max(1, min(passes, max(1, 8 // streams)))
-    n_break = n_break_passes * streams
-    r.reset_counters()
-    r.set_profiling(2)
-    r.set_pipelining(0)
-    r.run_samples(n_break_passes)
-    cb = r.counters()
-    r.set_profiling(0)
-    r.set_pipelining(args.pipelining)
+    cb = None
+    if args.full:
+        # untimed: per-stage breakdown (HIP events around every launch) over a few more samples, in serial
+        # order on one stream -- with the sample pipeline on, spans of the two streams overlap and a
+        # stage's span includes whatever ran beside it
+        n_break_passes = max(1, min(passes, max(1, 8 // streams)))
+        n_break = n_break_passes * streams
+        r.reset_counters()
+        r.set_profiling(2)
+        r.set_pipelining(0)
+        r.run_samples(n_break_passes)
+        cb = r.counters()
+        r.set_profiling(0)
+        r.set_pipelining(args.pipelining)
     if with_comm:
         rays_total, steps_total = r.allreduce_host([float(rays_local), float(steps)], op="sum")
         dt, t_reduce_max = r.allreduce_host([dt, t_reduce], op="max")
@@ -546,7 +555,7 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
     if rank == 0:
         import numpy as np
         img, wts, cnt, _ = r.read_accumulators()
-        # after the reduce every rank holds the sums of all ranks (and the breakdown pass added n_break samples)
+        # after the reduce every rank holds the sums of all ranks (and a breakdown pass added n_break samples)
         assert np.isfinite(img).all() and (cnt >= int(steps_total)).all(), "accumulators corrupt"
         # cl2_upload_scene stages the whole tree in LDS up to 512 records and 512 triangles
         in_lds = bool(r_org["tree_in_lds"])
@@ -558,20 +567,21 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
         k_ms, k_rays, k_launches = c["ms_traverse_conn"], c["rays_traverse_conn"], max(c["launches_traverse_conn"], 1)
         # (a launch of a handle with K sample streams carries the connection rays of K samples)
         avg_ms = k_ms / k_launches
-        alone_ms = cb["ms_traverse_conn"] / max(cb["launches_traverse_conn"], 1)
+        # the same launch alone on the machine: the serial breakdown pass (--full)
+        alone_ms = cb["ms_traverse_conn"] / max(cb["launches_traverse_conn"], 1) if cb else None
         rays_per_launch = k_rays / k_launches
         alg_gbs = rays_per_launch * b_ray / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        alg_gbs_alone = (cb["rays_traverse_conn"] / max(cb["launches_traverse_conn"], 1)) * b_ray / max(alone_ms * 1e-3, 1e-12) / 1e9
+        alg_gbs_alone = (cb["rays_traverse_conn"] / max(cb["launches_traverse_conn"], 1)) * b_ray / max(alone_ms * 1e-3, 1e-12) / 1e9 if cb else None
         pmc = static_pmc(scene_name, W, H, streams)
         traffic = pmc.get("hbm_bytes") if pmc else None
         lanes = pmc.get("thread_cycles_per_valu_inst") if pmc else None     # average active lanes per VALU wave-instruction
-        hbm = {"algorithmic_gbs": round(alg_gbs, 1), "algorithmic_gbs_launch_alone": round(alg_gbs_alone, 1),
+        hbm = {"algorithmic_gbs": round(alg_gbs, 1), "algorithmic_gbs_launch_alone": round(alg_gbs_alone, 1) if cb else None,
                "bytes_per_ray": round(b_ray, 1), "n_node": round(n_node, 3), "n_tri": round(n_tri, 3),
                "measured_gbs": round(traffic / (avg_ms * 1e-3) / 1e9, 1) if traffic and avg_ms > 0 else None,
                "measured_frac_of_peak": round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and avg_ms > 0 else None,
                "peak_gbs": HBM_PEAK_GBS}
         common = {"kernel": k_name, "rays_per_launch": round(rays_per_launch), "avg_launch_ms": round(avg_ms, 4),
-                  "avg_launch_ms_alone": round(alone_ms, 4), "traffic": traffic, "active_lanes_per_valu_inst": lanes,
+                  "avg_launch_ms_alone": round(alone_ms, 4) if cb else None, "traffic": traffic, "active_lanes_per_valu_inst": lanes,
                   "static": {"what": "PMC counters per launch (rocprofv3 --pmc passes of this command, committed; quoted only while the kernel sources hash to what was profiled)",
                              "source": pmc["source"], "sources_sha": pmc["sources_sha"]} if pmc else None}
         if in_lds:
@@ -581,7 +591,7 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
             frac = ach / VALU_PEAK_GINST if ach else None
             roof = {"bound": "valu", "achieved": round(ach, 1) if ach else None, "peak": round(VALU_PEAK_GINST, 1),
                     "unit": "G wave-instructions/s", "frac": round(frac, 4) if frac else None,
-                    "frac_launch_alone": round(n_valu / (alone_ms * 1e-3) / 1e9 / VALU_PEAK_GINST, 4) if n_valu and alone_ms > 0 else None,
+                    "frac_launch_alone": round(n_valu / (alone_ms * 1e-3) / 1e9 / VALU_PEAK_GINST, 4) if n_valu and alone_ms else None,
                     # the issue fraction counts instructions, not lanes: weighted by the lanes that were active in them
                     "lane_weighted_frac": round(frac * lanes / 64.0, 4) if frac and lanes else None,
                     "wave_insts_per_launch": n_valu, "cycles_per_wave_inst": 2.0, "hbm": hbm}
@@ -601,7 +611,7 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
                         "formula": "112 B x wide-node visits + 36 B x triangle records (round 6: the walk's own 36-byte records) + 32 B x binary records + 16 B x stack spills (write + read) + 48 B per ray (device tallies, cl2_set_counting(2))"}
             tree = org["tree_bytes"]
             roof = mesh_roofline(pmc, avg_ms, own_bytes(own and own["connection"], rays_per_launch), tree)
-            alone = mesh_roofline(pmc, alone_ms, None, tree)
+            alone = mesh_roofline(pmc, alone_ms, None, tree) if cb else None
             if roof is None:
                 # no PMC summary of these sources yet: nothing can be said about the bound (the contract figure below does not say it either)
                 roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "fractions": None,
@@ -615,7 +625,7 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
             # device's ray / node-test / triangle-test tallies equal the oracle's: tests/test_gpu_fullsize.py)
             roof["contract_algorithmic_gbs"] = round(alg_gbs, 1)
             roof["contract"] = {"bytes_per_ray": round(b_ray, 1), "n_node": round(n_node, 3), "n_tri": round(n_tri, 3),
-                                "algorithmic_gbs_launch_alone": round(alg_gbs_alone, 1),
+                                "algorithmic_gbs_launch_alone": round(alg_gbs_alone, 1) if cb else None,
                                 "served_from": ("L2 (32 MiB): the tree is %.1f MB" % (tree / 1e6)) if tree <= L2_BYTES else
                                                ("Infinity Cache (256 MiB) + L2: the tree is %.0f MB" % (tree / 1e6)) if tree <= IC_BYTES else "HBM",
                                 "algorithmic_over_fabric_traffic": round(rays_per_launch * b_ray / traffic, 3) if traffic else None}
@@ -627,11 +637,11 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
             sp = mesh_roofline(sp_row, sp_ms, own_bytes(own and own["subpath"], sp_rays), tree) or {"bound": None, "frac": None}
             # the same launches ALONE on the machine (serial breakdown pass): inside the pipeline they share the fabric with the
             # connection launch, and a fraction taken there says how the fabric is shared, not how far the walk is from its roof
-            sp_alone_ms = cb["ms_traverse_paths"] / max(cb["launches_traverse_paths"], 1)
-            sp_alone = mesh_roofline(sp_row, sp_alone_ms, None, tree)
+            sp_alone_ms = cb["ms_traverse_paths"] / max(cb["launches_traverse_paths"], 1) if cb else None
+            sp_alone = mesh_roofline(sp_row, sp_alone_ms, None, tree) if cb else None
             sp["frac_launch_alone"] = sp_alone["frac"] if sp_alone else None
             sp["fractions_launch_alone"] = {k: v["frac"] for k, v in sp_alone["fractions"].items()} if sp_alone else None
-            sp["avg_launch_ms_alone"] = round(sp_alone_ms, 4)
+            sp["avg_launch_ms_alone"] = round(sp_alone_ms, 4) if cb else None
             sp.update({"kernel": sp_row["name"] if sp_row else "k_traverse_wide<., PathRaySource>", "launches_per_pass": round(sp_launches / max(passes, 1), 2),
                        "avg_launch_ms": round(sp_ms, 4), "rays_per_launch": round(sp_rays),
                        "note": "avg_launch_ms is over ALL subpath traversal launches of the timed region (the merged level-0 launch included); "
@@ -646,7 +656,7 @@ def run_workload(args, scene_name, W, H, steps, warmup, rank, local_rank, world,
         out = {"scene_desc": scene_desc, "rays_total": rays_total, "rays_local": rays_local, "dt": dt, "roofline": roof,
                "steps_total": int(steps_total), "steps_rank": steps, "tuner_samples_in_warmup": tuned * streams, "paths_share": org["paths_share"],
                "comm": comm, "sample_streams": streams, "dumped": dumped,
-               "stages": {k[3:]: round(cb[k] / n_break, 4) for k in cb if k.startswith("ms_")}}
+               "stages": {k[3:]: round(cb[k] / n_break, 4) for k in cb if k.startswith("ms_")} if cb else None}
     r.close()
     return out
 
@@ -874,9 +884,12 @@ def main():
                     help="strong scaling: a FIXED number of samples split over the ranks (samples_for_rank) instead of --steps per rank")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the serial per-stage breakdown, the serial loop, the mesh legs (N = 1), "
+                         "the strong-scaling leg (N > 1) and the CPU baseline; the --no-* switches below trim it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-order-extra", action="store_true", help="skip the labelled nearest-first extras of the mesh legs (detail file only)")
-    ap.add_argument("--no-mesh", action="store_true", help="skip the mesh workloads (config 3 / 4 / 5 stand-ins) and the serial-loop figures of the N=1 line")
+    ap.add_argument("--no-mesh", action="store_true", help="--full without the mesh workloads (config 3 / 4 / 5 stand-ins) and the serial-loop figures of the N=1 line")
     ap.add_argument("--sample-streams", type=int, default=1,
                     help="sample streams of the headline workload (K independent samples of the frame per pass, cl2_set_sample_streams); "
                          "1 = the reference's single seed buffer per renderer")
@@ -945,7 +958,7 @@ def main():
     # (CLIVE2_BENCH_FORCE_STRONG=1: rehearsal of this leg on a one-rank communicator -- a second communicator in the same
     # process after the first one was destroyed; not used by the driver)
     want_strong = world > 1 or (with_comm and os.environ.get("CLIVE2_BENCH_FORCE_STRONG") == "1")
-    if want_strong and not strong and args.strong_spp > 0 and not args.no_mesh and args.scene == "cornell":
+    if args.full and want_strong and not strong and args.strong_spp > 0 and not args.no_mesh and args.scene == "cornell":
         # the strong-scaling form on the same job: BASELINE config 4 -- a FIXED number of samples of the
         # 82k-triangle scene split over the ranks, one all-reduce at the end
         from clive2_amd.distributed import samples_for_rank
@@ -989,8 +1002,9 @@ def main():
                        "parallelism": f"sample-split x{world}, one in-place RCCL all-reduce of the accumulators"
                                       if with_comm else "one GPU (no collective)"},
             "roofline": res["roofline"],
-            "stage_ms_per_step_serial": res["stages"],
         }
+        if res["stages"]:
+            out["stage_ms_per_step_serial"] = res["stages"]
         if res["comm"]:
             # what RCCL itself reported: `nranks` ranks on `distinct_devices` different GPUs (PCI addresses of all ranks)
             out["comm"] = res["comm"]
@@ -998,12 +1012,12 @@ def main():
             out["strong_scaling"] = strong_leg
         if res["dumped"]:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": res["dumped"]}
-        if world == 1 and not args.no_mesh:
+        if args.full and world == 1 and not args.no_mesh:
             try:
                 out["serial_run_sample_ms"] = serial_loop(args.scene, W, H, local_rank)
             except Exception as exc:                               # noqa: BLE001 -- an extra never costs the job its headline
                 out["serial_run_sample_ms"] = {"error": repr(exc)[:300]}
-        if world == 1 and not args.no_mesh and args.scene == "cornell":
+        if args.full and world == 1 and not args.no_mesh and args.scene == "cornell":
             # The other BASELINE.json configurations a single GPU holds, on the same line -- their tree is read through the caches,
             # and each leg says which resource binds its dominant launch (mesh_roofline): config 3 (5,136 triangles), config 4
             # (81,936), config 5 (1,003,536) at 1080p and at its own 3840 x 2160.  Their stage-share tuner runs in the warm-up
@@ -1018,7 +1032,7 @@ def main():
             for key, name, lw, lh, n_steps, k_leg in legs:
                 if n_steps > 0:
                     out[key] = mesh_leg(args, key, name, lw, lh, n_steps, k_leg, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_width, args.cpu_height, args.cpu_samples)
         emit(out, saved_stdout)
     os.close(saved_stdout)

@@ -1,5 +1,5 @@
 """bench.py --dump-outputs: the accumulators the timed region left, written as .npy files (float32 / float64, at most 64 MB,
-a seeded pixel sample above DUMP_MAX_PIXELS), and --steps as the exact number of timed samples."""
+a seeded pixel sample above DUMP_MAX_PIXELS), --steps as the exact number of timed samples, and what a plain run leaves to --full."""
 import json
 import os
 import subprocess
@@ -59,7 +59,8 @@ def test_dump_of_a_large_frame_is_a_fixed_seeded_sample_within_64_mb(tmp_path):
         assert np.array_equal(a[k], b[k])
 
 
-@pytest.mark.parametrize("argv", [["--steps", "0"], ["--steps", "3", "--sample-streams", "2"], ["--sample-streams", "0"]])
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--steps", "3", "--sample-streams", "2"], ["--sample-streams", "0"],
+                                  ["--full", "--steps", "0"]])
 def test_bench_refuses_steps_it_would_not_time_exactly(argv):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=60)
     assert p.returncode == 2 and p.stdout == "" and "must be" in p.stderr
@@ -87,3 +88,31 @@ def test_bench_dumps_the_timed_samples_identically_from_run_to_run(tmp_path):
         assert a[name].dtype == np.float32 and np.isfinite(a[name]).all()
         assert np.allclose(a[name], b[name], rtol=1e-5, atol=1e-7), name
     assert a["summed_image"].any()
+
+
+@pytest.mark.gpu
+def test_plain_run_does_only_the_headline_and_full_adds_the_rest(tmp_path):
+    """A plain run times the steps and prints the line, nothing else: no stage breakdown, serial loop, legs or CPU baseline.
+    `--full` adds them after the clock and changes nothing before or inside it: both runs dump the same accumulators."""
+    common = ["--width", "64", "--height", "48", "--steps", "3", "--warmup", "1"]
+    extra = {"plain": [], "full": ["--full", "--no-mesh", "--cpu-width", "64", "--cpu-height", "48", "--cpu-samples", "1"]}
+    lines, dumps = {}, {}
+    for kind, argv in extra.items():
+        d = tmp_path / kind
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + argv + ["--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines[kind] = json.loads(p.stdout)
+        dumps[kind] = _load(d)
+    plain, full = lines["plain"], lines["full"]
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup"):
+        assert plain[key] == full[key], key
+    assert plain["steps"] == 3 and plain["config"]["samples_rendered_all_ranks"] == 3
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["avg_launch_ms"] > 0
+    assert not {"stage_ms", "serial_ms", "legs", "cpu_baseline", "strong_scaling"} & set(plain)
+    assert "avg_launch_ms_alone" not in plain["roofline"]
+    assert {"stage_ms", "cpu_baseline"} <= set(full) and full["roofline"]["avg_launch_ms_alone"] > 0
+    assert "legs" not in full                                       # --no-mesh still trims --full
+    assert (dumps["plain"]["summed_sample_counts"] == 3).all() and (dumps["full"]["summed_sample_counts"] == 3).all()
+    for name in NAMES:
+        assert np.allclose(dumps["plain"][name], dumps["full"][name], rtol=1e-5, atol=1e-7), name

@@ -16,7 +16,7 @@ H=${6:-1080}
 TL="timeout -k 10 ${TLIM:-600}"
 OUT=gpurun_out
 mkdir -p $OUT
-B="bench.py --scene $SCENE --no-cpu-baseline --no-mesh --sample-streams $K --width $W --height $H"
+B="bench.py --full --scene $SCENE --no-cpu-baseline --no-mesh --sample-streams $K --width $W --height $H"
 echo $K > $OUT/pf_${SCENE}_streams.txt
 echo $STEPS > $OUT/pf_${SCENE}_steps.txt
 $TL rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/pf_${SCENE}_stats -o runc -- python3 $B --steps $STEPS --warmup 4 > $OUT/pf_${SCENE}_stats.log 2>&1

@@ -117,10 +117,10 @@ def main():
             timed = {"kernel": conn[0], "launches_in_timed_region": passes, "avg_ms": round(sum(e - b for b, e in t) / len(t) / 1e6, 4),
                      "serial_breakdown_launches": n_break, "alone_avg_ms": round(sum(e - b for b, e in a) / len(a) / 1e6, 4),
                      "all_launches": len(spans), "all_launches_avg_ms": round(sum(e - b for b, e in spans) / len(spans) / 1e6, 4),
-                     "what": "rocprofv3 --kernel-trace of `bench.py --scene ... --steps %d`: the launches of the timed region (pipelined), of the serial "
+                     "what": "rocprofv3 --kernel-trace of `bench.py --full --scene ... --steps %d`: the launches of the timed region (pipelined), of the serial "
                              "breakdown pass (alone) and of the whole process (tuner included: what the --stats average covers)" % steps}
     out = {"note": "rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ_*, TCC_* each in its own run, --kernel-trace only) of "
-                   f"`python3 bench.py --scene {scene} --no-cpu-baseline --no-mesh --sample-streams {streams} --width {W} --height {H} --steps 4 --warmup 1`; values are averages per launch "
+                   f"`python3 bench.py --full --scene {scene} --no-cpu-baseline --no-mesh --sample-streams {streams} --width {W} --height {H} --steps 4 --warmup 1`; values are averages per launch "
                    f"(a launch of a handle with {streams} sample stream(s) carries the rays of {streams} sample(s)); "
                    "FETCH_SIZE/WRITE_SIZE in KiB as reported; hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950 FETCH_SIZE half-count, "
                    "MI355X_MICROARCH.md HBM section); SQ_WAVE_CYCLES/SQ_WAIT_*/SQ_ACTIVE_INST_* are quad-cycles",
