@@ -83,7 +83,7 @@ EXPORTS = [
     "cl2_read_accumulators_packed", "cl2_write_accumulators_packed", "cl2_device_count", "cl2_synchronize",
     "cl2_comm_unique_id_bytes", "cl2_comm_get_unique_id", "cl2_comm_init_rank", "cl2_reduce_accumulators",
     "cl2_comm_allreduce_f64", "cl2_comm_destroy", "cl2_import_sample_images", "cl2_query_organisation", "cl2_set_profiling", "cl2_set_counting", "cl2_set_debug_flags", "cl2_read_counters",
-    "cl2_reset_counters", "cl2_selftest_exact_math", "cl2_export_rays", "cl2_export_paths", "cl2_export_aggregators",
+    "cl2_reset_counters", "cl2_selftest_exact_math", "cl2_export_rays", "cl2_export_paths", "cl2_export_aggregators", "cl2_export_connections",
     "cl2_export_sample_images", "cl2_probe_traverse", "cl2_probe_math", "cl2_probe_bounce",
     "cl2_tune", "cl2_set_subpath_gather", "cl2_comm_abort", "cl2_tone_log_sum", "cl2_tone_map",
     "cl2_set_sample_streams", "cl2_get_sample_streams", "cl2_set_export_stream", "cl2_comm_info",

@@ -1063,6 +1063,114 @@ __global__ __launch_bounds__(BLOCK) void k_traverse_conn(
     }
 }
 
+// k_connect_setup and k_traverse_conn in one launch, for trees wholly staged in LDS (the Cornell box).  There the global tag
+// queue buys nothing a workgroup cannot do for itself: its 256 pixels emit ~7,400 rays, 115 full wave passes, so a queue
+// local to the workgroup leaves under 1 % tail -- and the set-up launch, its global atomic, the 4-byte tags written and read
+// back and its second gather of both endpoints leave the connection stream's critical path.  The walk phase of one workgroup
+// overlaps the memory-bound cull phase of the others on the same CU.
+//   cull  the predicates of k_connect_setup (conn_ray on the same vertices: cmask is the same bits), with the light subpath
+//         in two batches of three vertices and the camera subpath one vertex at a time (t = 1 needs none), so that the
+//         kernel keeps the walk's 8 waves per SIMD (<= 64 VGPRs; k_connect_setup holds 12 vertices at once, 80 VGPRs);
+//   queue the live pairs as 2-byte LDS entries {slot << 8 | local pixel}, wave by wave and slot-major inside a wave (the
+//         order of k_connect_setup's tags), the base of a wave taken by an LDS atomic;
+//   walk  after one barrier all four waves walk the queue with full lanes: the ray and the closest-hit dispatch of
+//         k_traverse_conn, results through chit_store -- chit is the same bits by construction.
+// LDS: 36 x 256 x 2 B of queue + 256 B of specular flags + the staged tree (1 KB for the Cornell box): 8 workgroups per CU
+// fit in 160 KB.  SGPRs capped as in k_traverse_persistent: above 80, one workgroup in eight is not admitted.
+__global__ __launch_bounds__(BLOCK, 8) __attribute__((amdgpu_num_sgpr(78))) void k_connect_walk_lds(
+        BvhView bvh, int B, PathBufs lp, PathBufs cp, const MaterialDev* __restrict__ mats, int n_mats, CameraRec cam,
+        unsigned long long* __restrict__ cmask, float2* __restrict__ chit, Stats* stats) {
+    __shared__ unsigned short s_queue[CONN_SLOTS * BLOCK];
+    __shared__ unsigned char s_spec[256];                  // material type > 0 (the table has at most 256 entries)
+    __shared__ unsigned s_count;
+    for (int i = threadIdx.x; i < n_mats; i += BLOCK) s_spec[i] = __float_as_int(mats[i].color_type.w) > 0;
+    if (threadIdx.x == 0) s_count = 0;
+    BvhLds lds{nullptr, nullptr};
+    stage_bvh(lds, bvh);                                   // its barrier also publishes s_spec and s_count
+    const int pid = blockIdx.x * BLOCK + threadIdx.x;
+    const bool valid = pid < B;
+    const int Lc = valid ? cp.len[pid] : 0, Ll = valid ? lp.len[pid] : 0;
+    const V3 focal = cam3(cam.focal_point), cam_dir = cam3(cam.direction);
+
+    // cull phase; wave-decided loads indexed by clamped_pid (lanes behind the end of the frame read pixel 0's records)
+    const size_t vB = (size_t)B, lpid = clamped_pid(valid, pid);
+    ConnVtx lv[MAX_VERTS];
+    unsigned l_spec = 0;
+#pragma unroll
+    for (int sb = 0; sb < MAX_VERTS; sb += 3) {
+        float4 la[3], lc[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            if (__builtin_amdgcn_ballot_w64(sb + k < Ll) != 0ull) { la[k] = lp.P0[(sb + k) * vB + lpid]; lc[k] = lp.P2[(sb + k) * vB + lpid]; }
+            else la[k] = lc[k] = make_float4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int s = sb + k;
+            lv[s] = ConnVtx{v3(0, 0, 0), v3(0, 0, 0), 0};
+            if (s < Ll) {
+                lv[s] = ConnVtx{v3(la[k]), v3(lc[k]), 0};
+                if (s_spec[__float_as_int(lc[k].w) & 0xFF]) l_spec |= 1u << s;
+            }
+        }
+    }
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int t = 1; t <= MAX_VERTS; t++) {
+        ConnVtx cv{v3(0, 0, 0), v3(0, 0, 0), 0};
+        bool c_specular = false;
+        if (t > 1) {                                       // conn_ray does not look at the camera vertex for t = 1
+            float4 ca = make_float4(0, 0, 0, 0), cc = make_float4(0, 0, 0, 0);
+            if (__builtin_amdgcn_ballot_w64(t <= Lc) != 0ull) { ca = cp.P0[(t - 1) * vB + lpid]; cc = cp.P2[(t - 1) * vB + lpid]; }
+            if (t <= Lc) {
+                cv = ConnVtx{v3(ca), v3(cc), 0};
+                c_specular = s_spec[__float_as_int(cc.w) & 0xFF];
+            }
+        }
+#pragma unroll
+        for (int s = 1; s <= MAX_VERTS; s++) {
+            V3 dir;
+            const bool pred = (t <= Lc) && (s <= Ll) && conn_ray(t, lv[s - 1], cv, (l_spec >> (s - 1)) & 1u, c_specular, focal, cam_dir, dir);
+            if (pred) mine |= 1ull << conn_slot(t, s);
+        }
+    }
+    if (valid) cmask[pid] = mine;
+
+    // local queue: this wave's entries from an LDS atomic base, slot-major
+    unsigned wave_total = __popcll(mine);
+    for (int off = 32; off > 0; off >>= 1) wave_total += __shfl_xor(wave_total, off);
+    unsigned running = 0;
+    if (wave_lane() == 0) running = atomicAdd(&s_count, wave_total);
+    running = __builtin_amdgcn_readfirstlane(__shfl(running, 0));
+#pragma unroll
+    for (int slot = 0; slot < CONN_SLOTS; slot++) {
+        const bool pred = (mine >> slot) & 1ull;
+        const unsigned long long m = __ballot(pred);
+        if (pred) s_queue[running + rank_below(m)] = (unsigned short)((slot << 8) | threadIdx.x);
+        running += __popcll(m);
+    }
+    __syncthreads();
+
+    // walk phase
+    const unsigned n = s_count;
+    unsigned nb = 0, nt = 0;
+    for (unsigned j = threadIdx.x; j < n; j += BLOCK) {
+        const unsigned e = s_queue[j];
+        const int slot = (int)(e >> 8), p = blockIdx.x * BLOCK + (int)(e & 0xFF);
+        const int t = slot / 6 + 1, s = slot % 6 + 1;
+        const V3 o = v3(lp.P0[(size_t)(s - 1) * B + p]);
+        V3 target = focal;
+        if (t > 1) target = v3(cp.P0[(size_t)(t - 1) * B + p]);
+        const V3 d = normalize(target - o);
+        const Hit h = closest_hit<false>(lds, bvh, o, d, rcp3(d), nb, nt);
+        chit_store(chit, B, slot, p, h.tri, h.t);
+    }
+    if (threadIdx.x == 0 && n) {
+        atomicAdd(&stats->rays, (unsigned long long)n);
+        atomicAdd(&stats->conn_rays, (unsigned long long)n);
+    }
+}
+
 // Aggregator SoA rows: 0..8 weights[i][j] (row i*3+j), 9..11 total_contribution, 12 contrib_weight_sum.
 constexpr int AGG_ROWS = 13;
 

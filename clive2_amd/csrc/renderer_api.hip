@@ -286,6 +286,12 @@ inline bool split_paths(const cl2_renderer* r) {
 inline bool split_conn(const cl2_renderer* r) {
     return r->traversal_mode >= 2 || (r->traversal_mode == 0 && !tree_in_lds(r));
 }
+// Connection set-up and walk fused into one launch (k_connect_walk_lds): trees wholly staged in LDS whose pruned table is a
+// flat list of leaves (closest_hit_flat), one ray per lane, not while counting.  Debug bit 25 keeps the two launches (A/B).
+inline bool fused_conn(const cl2_renderer* r) {
+    return tree_in_lds(r) && !split_conn(r) && !count_ref(r) && r->bvh.n_fast_nodes > 0 && r->bvh.fast_flat &&
+           !((r->debug_flags >> 25) & 1);
+}
 // The exact 4-wide walk (bvh_wide.hpp) for the connection-ray launch and, while the sample pipeline runs, the per-level subpath
 // launches: mode 5, and the automatic choice for every tree that is read through the caches.  Round 2 kept the binary walk above
 // 16 MB (15.7 vs 18.6 ms on the 155 MB tree, one triangle per pass); with two triangle pairs per pass, 7 stack entries in LDS and
@@ -536,6 +542,15 @@ int launch_connect(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs)
     const int B = r->B;
     const PathBufs& lp = set[CL2_LIGHT];
     const PathBufs& cp = set[CL2_CAMERA];
+    if (fused_conn(r)) {
+        // one launch: cull, workgroup-local queue, walk (k_connect_walk_lds); the set-up stage takes no time of its own
+        Timed t(r, ST_TRAVERSE_CONN, st);
+        hipLaunchKernelGGL(k_connect_walk_lds, dim3(grid_for(B)), dim3(BLOCK), bvh_lds_bytes(r), st, r->bvh, B, lp, cp,
+                           r->d_mats, r->n_mats, r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_stats);
+        r->launches_tc++;
+        HIP_TRY(r, hipGetLastError());
+        return CL2_OK;
+    }
     HIP_TRY(r, hipMemsetAsync(r->d_qcount + 7, 0, sizeof(unsigned), st));
     {
         Timed t(r, ST_CONNECT_SETUP, st);
@@ -1767,6 +1782,18 @@ int cl2_export_aggregators(cl2_renderer* r, void* out, size_t n_records) {
     if (rc == CL2_OK && hipMemcpy(out, d, (size_t)r->FB * 128, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(r, CL2_E_HIP, "export copy failed");
     dev_free(r, d);
     return rc;
+}
+
+int cl2_export_connections(cl2_renderer* r, uint64_t* cmask, int32_t* tri, float* t1, size_t n_pixels) {
+    STAGE_PROLOGUE(r);
+    if (n_pixels != (size_t)r->B) return fail(r, CL2_E_INVALID, "n_pixels must equal the batch size");
+    TRY(drain(r));
+    const size_t B = r->B;
+    if (cmask) HIP_TRY(r, hipMemcpy(cmask, r->d_cmask[0], B * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (tri) HIP_TRY(r, hipMemcpy(tri, r->d_chit[0], (size_t)CONN_SLOTS * B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (t1) HIP_TRY(r, hipMemcpy(t1, reinterpret_cast<const float*>(r->d_chit[0]) + (size_t)CONN_SLOTS * B,
+                                 (size_t)MAX_VERTS * B * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 int cl2_export_sample_images(cl2_renderer* r, float* fin4, float* light4, float* sw, float* uni4, size_t n_pixels) {

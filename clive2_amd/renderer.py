@@ -414,6 +414,16 @@ class Renderer:
         self._check(self._L.cl2_export_aggregators(self._h, ptr(out), C.c_size_t(len(out))), "export_aggregators")
         return out
 
+    def export_connections(self):
+        """Connection stage of the last join_paths: cmask (uint64 per pixel), hit triangle per strategy pair (int32 [36, B],
+        meaningful where the pair's cmask bit is set) and hit distance of the t = 1 pairs (float32 [6, B])."""
+        B = self.batch_size
+        cmask = np.zeros(B, np.uint64)
+        tri = np.zeros((36, B), np.int32)
+        t1 = np.zeros((6, B), np.float32)
+        self._check(self._L.cl2_export_connections(self._h, ptr(cmask), ptr(tri), ptr(t1), C.c_size_t(B)), "export_connections")
+        return cmask, tri, t1
+
     def export_sample_images(self):
         B = self.batch_size
         fin, light, uni = (np.zeros((B, 4), np.float32) for _ in range(3))

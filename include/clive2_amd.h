@@ -295,11 +295,14 @@ int cl2_read_walk_tallies(cl2_renderer* r, cl2_walk_tallies* out);
  *   bits 16-19  accepted and ignored (round 3: stack entries per lane in LDS of the 4-wide walk; a compile-time 8 since round 4)
  *   bits 20-23  4-wide walk: LDS window of the top of the wide tree in units of 32 nodes (0 = by tree size: 32 nodes, 64 when
  *               the tree streams from memory; 15 = no window)
+ *   bit 25      connection rays of a tree wholly staged in LDS with a flat pruned table: the set-up launch and the walk
+ *               launch over a global tag queue (csrc/kernels.hpp: k_connect_setup, k_traverse_conn) instead of the fused
+ *               launch with a workgroup-local queue (k_connect_walk_lds), for A/B runs and tests
  * Any other bit is refused (CL2_E_INVALID).  Bits 0-2 exist ONLY in the test variant of the library
  * (libclive2_amd_test.so, -DCL2_TEST_VARIANT), where they switch parts of the resolve stage off for timing
  * dissections -- bit 0 the t = 1 splat atomics, bit 1 / bit 2 the t >= 2 / t == 1 strategy pairs -- and make the
  * render INVALID; the shipped library refuses them. */
-#define CL2_DEBUG_KNOWN_BITS 0x00FF7FFF
+#define CL2_DEBUG_KNOWN_BITS 0x02FF7FFF
 int cl2_set_debug_flags(cl2_renderer* r, int flags);
 /* Reproducible light image, off by default.  The reference's light-image chain (sort by target pixel, per-pixel gather:
  * src/renderer.py:97-111, :213-250, src/trace.metal:872-964) is deterministic; the float atomics that replace it add a pixel's
@@ -346,6 +349,10 @@ int cl2_probe_bounce(cl2_renderer* r, int from_camera, const float* in, size_t n
 int cl2_export_rays(cl2_renderer* r, int which, void* out_rays, size_t n_records);        /* Ray[batch]  */
 int cl2_export_paths(cl2_renderer* r, int which, void* out_paths, size_t n_records);      /* Path[batch] */
 int cl2_export_aggregators(cl2_renderer* r, void* out, size_t n_records);                 /* 128-B stride */
+/* the connection stage's results of the last join_paths: per pixel the strategy-pair mask (bit (t-1)*6 + (s-1): the pair
+ * passed the culls and has a ray), the closest-hit triangle of every pair (int32[36][n_pixels], slot-major; meaningful where
+ * the mask bit is set) and the hit distance of the six t = 1 pairs (float[6][n_pixels]).  Any pointer may be NULL. */
+int cl2_export_connections(cl2_renderer* r, uint64_t* cmask, int32_t* tri, float* t1, size_t n_pixels);
 /* per-sample images: finalized_samples (float4), out_light_image rgb + summed light weight (float4),
  * sample_weights (K6 value only), out_camera_image (float4).  Any pointer may be NULL. */
 int cl2_export_sample_images(cl2_renderer* r, float* finalized4, float* light4, float* sample_weights,

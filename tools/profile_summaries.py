@@ -96,10 +96,12 @@ def main():
         if row.get("SQ_THREAD_CYCLES_VALU") and row.get("SQ_INSTS_VALU"):
             row["thread_cycles_per_valu_inst"] = round(row["SQ_THREAD_CYCLES_VALU"] / row["SQ_INSTS_VALU"], 2)
     # the connection-ray traversal launch: the 4-wide walk where the scene uses it (its left-over launch of the binary
-    # kernel carries a handful of rays), else the binary persistent walk, else the LDS kernel of the small scenes
+    # kernel carries a handful of rays), else the binary persistent walk, else the LDS kernels of the small scenes -- the fused
+    # set-up + walk where the pruned table is flat (the Cornell box), else k_traverse_conn
     # (k_traverse_wide<REPS, Source, TALLY, SPEC>: the tallying variant runs in the warm-up's counting pass only and is not the launch)
     conn = ([k for k in kernels if k.startswith("k_traverse_wide<") and "ConnRaySource,false" in k] or
             [k for k in kernels if k.startswith("k_traverse_persistent<false") and "ConnRaySource" in k] or
+            [k for k in kernels if k == "k_connect_walk_lds"] or
             [k for k in kernels if k.startswith("k_traverse_conn<false")])
     # The --stats average of a kernel covers EVERY launch of the process: the share tuner's 54 passes (other grid shares: slower launches),
     # the timed region, the serial-order breakdown pass.  What bench.py's live `avg_launch_ms` must agree with is the timed region's
