@@ -91,6 +91,8 @@ EXPORTS = [
     "cl2_render_features", "cl2_read_features", "cl2_denoise",
     "cl2_set_error_tracking", "cl2_get_error_tracking", "cl2_read_moments_packed", "cl2_write_moments_packed",
     "cl2_read_standard_error", "cl2_relative_error", "cl2_run_until",
+    "cl2_set_sample_density", "cl2_read_sample_density", "cl2_update_sample_density", "cl2_set_adaptive_sampling",
+    "cl2_get_adaptive_sampling", "cl2_read_camera_samples",
 ]
 
 
@@ -167,6 +169,12 @@ def lib(variant=None):
         L.cl2_relative_error.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double)]
         L.cl2_run_until.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                     C.POINTER(C.c_double)]
+        L.cl2_set_sample_density.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_read_sample_density.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_update_sample_density.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        L.cl2_set_adaptive_sampling.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.cl2_get_adaptive_sampling.argtypes = [C.c_void_p]
+        L.cl2_read_camera_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         for name in ("cl2_reduce_accumulators", "cl2_comm_destroy", "cl2_comm_abort", "cl2_synchronize"):
             getattr(L, name).argtypes = [C.c_void_p]
         _libs[variant] = L

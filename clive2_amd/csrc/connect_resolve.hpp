@@ -217,13 +217,15 @@ __device__ __forceinline__ void resolve_pair(
     }
 }
 
-template <int WAVES_PER_SIMD, bool MATS_LDS, bool DET = false>
+// MAPPED (adaptive sampling, adaptive.hpp): the pixel of the filter weights is the slot map's map[pid] instead of pid % (W*H);
+// nothing else in the kernel takes an image pixel from a slot (the t = 1 splat takes only its plane base from it).
+template <int WAVES_PER_SIMD, bool MATS_LDS, bool DET = false, bool MAPPED = false>
 __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_connect_resolve(
         int B, PathBufs lp, PathBufs cp, const MaterialDev* __restrict__ mats_g, int n_mats,
         const float4* __restrict__ tri_shade, CamTris cam_tris, CameraRec cam, const unsigned long long* __restrict__ cmask,
         const float2* __restrict__ chit, float* __restrict__ agg, float4* __restrict__ light_image,
         float4* __restrict__ uni_out, Stats* stats, int debug_flags,
-        unsigned* __restrict__ det_keys, float4* __restrict__ det_vals) {
+        unsigned* __restrict__ det_keys, float4* __restrict__ det_vals, const int* __restrict__ map) {
     __shared__ float GCs[(MAX_VERTS - 1) * BLOCK];     // GC[v] = G(camera[v], camera[v+1])
     __shared__ float RCs[(MAX_VERTS - 1) * BLOCK];     // RC[m]: ratio of camera vertex m with both neighbours on the camera side
     __shared__ float LNs[3 * MAX_VERTS * BLOCK];       // light vertex normals
@@ -365,7 +367,9 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_connect_resolve(
 
     // ---- reconstruction-filter weights, trace.metal:827-862.  A zero-length camera path is the
     // reference's zero-filled Path: pixel 0, film point (0,0,0). ----
-    const int pixel_idx = (Lc > 0) ? pid % (cam.pixel_width * cam.pixel_height) : 0;
+    int pixel_idx = 0;
+    if constexpr (MAPPED) { if (Lc > 0) pixel_idx = map[pid]; }
+    else pixel_idx = (Lc > 0) ? pid % (cam.pixel_width * cam.pixel_height) : 0;
     V3 film = v3(0, 0, 0);
     if (Lc > 0) film = v3(cp.P0[pid]);
     const float ppw = cam.phys_width / cam.pixel_width, pph = cam.phys_height / cam.pixel_height;

@@ -144,10 +144,14 @@ __global__ __launch_bounds__(BLOCK) void k_gen_light_rays(
 // trace.metal:1020-1067 with indices[id] == id (renderer.py:92-94).
 // The ray of entry `id` alone: two draws of its xorshift state, the jittered film point and the direction to the focal
 // point.  Shared with the first-hit feature pass (denoise.hpp), which must cast exactly these rays.
-__device__ __forceinline__ void camera_ray(int id, const CameraRec& c, uint32_t& seed0, uint32_t& seed1, V3& origin, V3& dir) {
+// MAPPED (adaptive sampling, adaptive.hpp): the pixel of entry `id` is map[id]; <false> is the default path (and the feature pass)
+// and compiles to the same instructions as before the parameter existed (`map` is not read).
+template <bool MAPPED = false>
+__device__ __forceinline__ void camera_ray(int id, const CameraRec& c, uint32_t& seed0, uint32_t& seed1, V3& origin, V3& dir,
+                                           const int* __restrict__ map = nullptr) {
     const float x_offset = xorshift_random(seed0);
     const float y_offset = xorshift_random(seed1);
-    const int pix = id % (c.pixel_width * c.pixel_height);          // the pixel of entry `id` (sample streams: see the header)
+    const int pix = MAPPED ? map[id] : id % (c.pixel_width * c.pixel_height);   // the pixel of entry `id` (sample streams: see the header)
     const int pixel_x = pix % c.pixel_width, pixel_y = pix / c.pixel_width;
     const float xn = (pixel_x + x_offset - 0.5f * c.pixel_width) / (float)c.pixel_width;
     const float yn = (pixel_y + y_offset - 0.5f * c.pixel_height) / (float)c.pixel_height;
@@ -157,9 +161,11 @@ __device__ __forceinline__ void camera_ray(int id, const CameraRec& c, uint32_t&
     dir = normalize(cam3(c.focal_point) - origin);
 }
 
-__device__ __forceinline__ void gen_camera_ray(int id, const CameraRec& c, uint32_t& seed0, uint32_t& seed1, const PathBufs& pb) {
+template <bool MAPPED>
+__device__ __forceinline__ void gen_camera_ray(int id, const CameraRec& c, uint32_t& seed0, uint32_t& seed1, const PathBufs& pb,
+                                               const int* __restrict__ map) {
     V3 origin, dir;
-    camera_ray(id, c, seed0, seed1, origin, dir);
+    camera_ray<MAPPED>(id, c, seed0, seed1, origin, dir, map);
     const float c_imp = 1.0f / (c.phys_width * c.phys_height);
     pb.P0[id] = f4(origin, c_imp);
     pb.P1[id] = f4(dir, 1.0f);                    // l_importance "filled in later"
@@ -170,26 +176,31 @@ __device__ __forceinline__ void gen_camera_ray(int id, const CameraRec& c, uint3
     pb.carry[id] = c_imp;                         // new_ray.c_importance, trace.metal:404
 }
 
-__global__ __launch_bounds__(BLOCK) void k_gen_camera_rays(int B, CameraRec c, uint2* __restrict__ seeds, PathBufs pb) {
+template <bool MAPPED>
+__global__ __launch_bounds__(BLOCK) void k_gen_camera_rays(int B, CameraRec c, uint2* __restrict__ seeds, PathBufs pb,
+                                                           const int* __restrict__ map) {
     const int id = blockIdx.x * BLOCK + threadIdx.x;
     if (id >= B) return;
     uint2 sd = seeds[id];
     uint32_t seed0 = sd.x, seed1 = sd.y;
-    gen_camera_ray(id, c, seed0, seed1, pb);
+    gen_camera_ray<MAPPED>(id, c, seed0, seed1, pb, map);
     seeds[id] = make_uint2(seed0, seed1);
 }
 
 // K1 then K2 for the same pixel in one launch (cl2_run_samples): the pixel's RNG state goes from the light-ray draws to
 // the camera-ray draws in registers, as make_light_rays followed by make_camera_rays leaves it (renderer.py:281-283).
+// Light paths are generated per entry from that entry's seed, independently of the pixel its camera ray samples.
+template <bool MAPPED>
 __global__ __launch_bounds__(BLOCK) void k_gen_rays(
         int B, const float4* __restrict__ light_tris, const float* __restrict__ light_areas, const int* __restrict__ light_tri_index,
-        const MaterialDev* __restrict__ mats, int light_count, CameraRec c, uint2* __restrict__ seeds, PathBufs lp, PathBufs cp) {
+        const MaterialDev* __restrict__ mats, int light_count, CameraRec c, uint2* __restrict__ seeds, PathBufs lp, PathBufs cp,
+        const int* __restrict__ map) {
     const int id = blockIdx.x * BLOCK + threadIdx.x;
     if (id >= B) return;
     uint2 sd = seeds[id];
     uint32_t seed0 = sd.x, seed1 = sd.y;
     gen_light_ray(id, light_tris, light_areas, light_tri_index, mats, light_count, seed0, seed1, lp);
-    gen_camera_ray(id, c, seed0, seed1, cp);
+    gen_camera_ray<MAPPED>(id, c, seed0, seed1, cp, map);
     seeds[id] = make_uint2(seed0, seed1);
 }
 

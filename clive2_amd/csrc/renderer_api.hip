@@ -21,6 +21,7 @@
 #include "kernels.hpp"
 #include "denoise.hpp"
 #include "error_estimate.hpp"
+#include "adaptive.hpp"
 #include "tonemap.hpp"
 #include "det_splat.hpp"
 #include "bvh_builder.hpp"
@@ -151,6 +152,24 @@ struct cl2_renderer {
     bool mom_valid = false;              // every addend in the accumulators also went into the moments
     bool acc_clean = true;               // the accumulators hold nothing (cl2_create, cl2_reset_accumulators)
     double* d_err_partial = nullptr;     // frame metric: [3][ERR_BLOCKS] per-workgroup partials + [4] result (first call)
+
+    // adaptive sampling (cl2_set_sample_density, adaptive.hpp): the density's buffers exist while one is set (`density`), W*H
+    // entries each; the maps have one per subpath buffer set, B entries each (they are written and read with the set's pass)
+    bool density = false;                // a density is set explicitly: run_chunk takes the mapped kernels
+    uint64_t* d_dens_C = nullptr;        // inclusive prefix sum of the quantised density M (units of 2^-16)
+    uint64_t* d_dens_M = nullptr;        // M before the scan (quantisation scratch)
+    float* d_dens_invm = nullptr;        // 1/m_q = (float)(2^16 / M_q): the factor of every camera sample of pixel q
+    float* d_dens_m = nullptr;           // the density being quantised (caller's weights or the update's m)
+    double* d_dens_partial = nullptr;    // [3][DENS_BLOCKS] per-workgroup partials + [3] totals
+    unsigned long long* d_dens_fsum = nullptr;
+    void* d_dens_tmp = nullptr;          // rocPRIM scan scratch
+    size_t dens_tmp_bytes = 0;
+    int* d_map[3] = {nullptr, nullptr, nullptr};   // slot -> pixel of every plane, one per subpath buffer set
+    unsigned* d_cam_count = nullptr;     // camera samples received by mapped passes since cl2_reset_accumulators (first density)
+    uint64_t cam_uniform = 0;            // ... and per pixel by unmapped passes (one per stream and pass)
+    uint32_t dens_pass = 0;              // passes rendered with a density: the input of the slot offsets' hash (never reset)
+    bool adaptive = false;               // cl2_set_adaptive_sampling: cl2_run_until updates the density before every chunk
+    double adaptive_share = 0.25;
 };
 
 namespace {
@@ -247,16 +266,22 @@ int launch_generate(cl2_renderer* r, int which, hipStream_t st, const PathBufs* 
         hipLaunchKernelGGL(k_gen_light_rays, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->d_light_tris,
                            r->d_light_areas, r->d_light_tri_index, r->d_mats, r->light_count, r->d_seeds, set[CL2_LIGHT]);
     else
-        hipLaunchKernelGGL(k_gen_camera_rays, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->cam, r->d_seeds,
-                           set[CL2_CAMERA]);
+        hipLaunchKernelGGL(k_gen_camera_rays<false>, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->cam, r->d_seeds,
+                           set[CL2_CAMERA], (const int*)nullptr);
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
 }
 
-int launch_generate_both(cl2_renderer* r, hipStream_t st, const PathBufs* set) {
+// `map`: the set's slot -> pixel map of a mapped pass (adaptive.hpp), nullptr = the default kernels
+int launch_generate_both(cl2_renderer* r, hipStream_t st, const PathBufs* set, const int* map) {
     Timed t(r, ST_GENERATE, st);
-    hipLaunchKernelGGL(k_gen_rays, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->d_light_tris, r->d_light_areas,
-                       r->d_light_tri_index, r->d_mats, r->light_count, r->cam, r->d_seeds, set[CL2_LIGHT], set[CL2_CAMERA]);
+    if (map)
+        hipLaunchKernelGGL(k_gen_rays<true>, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->d_light_tris, r->d_light_areas,
+                           r->d_light_tri_index, r->d_mats, r->light_count, r->cam, r->d_seeds, set[CL2_LIGHT], set[CL2_CAMERA], map);
+    else
+        hipLaunchKernelGGL(k_gen_rays<false>, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->d_light_tris, r->d_light_areas,
+                           r->d_light_tri_index, r->d_mats, r->light_count, r->cam, r->d_seeds, set[CL2_LIGHT], set[CL2_CAMERA],
+                           (const int*)nullptr);
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
 }
@@ -629,16 +654,17 @@ int ensure_det_buffers(cl2_renderer* r) {
     return CL2_OK;
 }
 
-int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs) {
+int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs, const int* map = nullptr) {
     const int B = r->B;
     const PathBufs& lp = set[CL2_LIGHT];
     const PathBufs& cp = set[CL2_CAMERA];
     {
         Timed t(r, ST_CONNECT_RESOLVE, st);
-#define CL2_RESOLVE(W, ML, DET)                                                                                                  \
-        hipLaunchKernelGGL((k_connect_resolve<W, ML, DET>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, \
+#define CL2_RESOLVE_M(W, ML, DET, MAPPED)                                                                                        \
+        hipLaunchKernelGGL((k_connect_resolve<W, ML, DET, MAPPED>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, \
                            r->cam_tris, r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_agg, r->d_light_image, r->d_uni, r->d_stats, r->debug_flags, \
-                           r->d_det_keys, r->d_det_vals)
+                           r->d_det_keys, r->d_det_vals, map)
+#define CL2_RESOLVE(W, ML, DET) do { if (map) CL2_RESOLVE_M(W, ML, DET, true); else CL2_RESOLVE_M(W, ML, DET, false); } while (0)
         // 3 waves per SIMD: what 165 VGPRs and 52 KB of LDS tables per workgroup allow (2 / 4 measured slower: DESIGN 6.1).  Debug
         // bits 4-6 = 7: one wave per camera vertex (tests/connect_resolve_wide.hpp: same results bit for bit, measured slower: 1.14 vs
         // 0.93 ms; a second implementation kept as a cross-check, built only with -DCL2_TEST_VARIANT = libclive2_amd_test.so)
@@ -647,6 +673,7 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs)
         if (occ == 7 && r->streams != 1) return fail(r, CL2_E_INVALID, "the cross-check resolve kernel handles one sample stream");
         // (it splats with atomics and writes no records: the sort + gather below would read buffers it never filled)
         if (occ == 7 && r->reproducible) return fail(r, CL2_E_INVALID, "the cross-check resolve kernel has no reproducible form: clear debug bits 4-6 or cl2_set_reproducible(0)");
+        if (occ == 7 && r->density) return fail(r, CL2_E_STATE, "the cross-check resolve kernel has no mapped form: cl2_set_sample_density(NULL) or clear debug bits 4-6");
 #ifdef CL2_TEST_VARIANT
         if (occ == 7)
             hipLaunchKernelGGL(k_connect_resolve_wide, dim3((B + RW_PIX - 1) / RW_PIX), dim3(RW_BLOCK), 0, st, B, lp, cp, r->d_mats,
@@ -668,6 +695,7 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs)
             if (r->n_mats <= LDS_MAT_CAP) CL2_RESOLVE(3, true, false); else CL2_RESOLVE(2, false, false);
         }
 #undef CL2_RESOLVE
+#undef CL2_RESOLVE_M
     }
     HIP_TRY(r, hipGetLastError());
     if (r->reproducible) {
@@ -707,9 +735,17 @@ int launch_accumulate(cl2_renderer* r, hipStream_t st) {
     return CL2_OK;
 }
 
-int launch_finalize_accumulate(cl2_renderer* r, hipStream_t st) {
+// `mapped`: the pass ran with the density's slot maps, `pass` = its number (adaptive.hpp)
+int launch_finalize_accumulate(cl2_renderer* r, hipStream_t st, bool mapped = false, uint32_t pass = 0) {
     Timed t(r, ST_FINALIZE, st);
-    if (r->d_mom)
+    if (mapped) {
+        if (r->d_mom)
+            hipLaunchKernelGGL(k_finalize_accumulate_mapped<true>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
+                               r->d_light_image, r->d_uni, r->d_acc, r->d_mom, r->d_dens_C, r->d_dens_invm, pass, r->d_cam_count);
+        else
+            hipLaunchKernelGGL(k_finalize_accumulate_mapped<false>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
+                               r->d_light_image, r->d_uni, r->d_acc, (float*)nullptr, r->d_dens_C, r->d_dens_invm, pass, r->d_cam_count);
+    } else if (r->d_mom)
         hipLaunchKernelGGL(k_finalize_accumulate<true>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
                            r->d_light_image, r->d_uni, r->d_acc, r->d_mom);
     else
@@ -745,6 +781,7 @@ void free_pixel_state(cl2_renderer* r) {
     for (int q = 0; q < 2; q++) { dev_free(r, r->d_chit[q]); dev_free(r, r->d_cmask[q]); }
     dev_free(r, r->d_agg); dev_free(r, r->d_light_image); dev_free(r, r->d_finalized); dev_free(r, r->d_uni);
     dev_free(r, r->d_sample_w); dev_free(r, r->d_block_stats);
+    for (int q = 0; q < 3; q++) dev_free(r, r->d_map[q]);
 }
 
 int alloc_pixel_state(cl2_renderer* r) {
@@ -795,6 +832,13 @@ int alloc_pixel_state(cl2_renderer* r) {
     do {                                  \
         int rc_ = need_scene(r);          \
         if (rc_ != CL2_OK) return rc_;    \
+    } while (0)
+
+// the stage calls (cl2_make_light_rays ... cl2_process_images) have no mapped form: refused while a density is set
+#define STAGE_CALL_PROLOGUE(r)                                                                                              \
+    do {                                                                                                                  \
+        STAGE_PROLOGUE(r);                                                                                                \
+        if ((r)->density) return fail((r), CL2_E_STATE, "the stage calls have no mapped form: cl2_set_sample_density(NULL) first"); \
     } while (0)
 
 }  // namespace
@@ -1029,24 +1073,25 @@ int cl2_set_export_stream(cl2_renderer* r, int stream) {
     return CL2_OK;
 }
 
-int cl2_make_light_rays(cl2_renderer* r) { STAGE_PROLOGUE(r); TRY(launch_generate(r, CL2_LIGHT, r->stream, r->sets[r->cur])); return drain(r); }
-int cl2_make_camera_rays(cl2_renderer* r) { STAGE_PROLOGUE(r); TRY(launch_generate(r, CL2_CAMERA, r->stream, r->sets[r->cur])); return drain(r); }
-int cl2_trace_light_rays(cl2_renderer* r) { STAGE_PROLOGUE(r); TRY(launch_subpaths(r, r->stream, r->sets[r->cur], 1)); return drain(r); }
-int cl2_trace_camera_rays(cl2_renderer* r) { STAGE_PROLOGUE(r); TRY(launch_subpaths(r, r->stream, r->sets[r->cur], 2)); return drain(r); }
+int cl2_make_light_rays(cl2_renderer* r) { STAGE_CALL_PROLOGUE(r); TRY(launch_generate(r, CL2_LIGHT, r->stream, r->sets[r->cur])); return drain(r); }
+int cl2_make_camera_rays(cl2_renderer* r) { STAGE_CALL_PROLOGUE(r); TRY(launch_generate(r, CL2_CAMERA, r->stream, r->sets[r->cur])); return drain(r); }
+int cl2_trace_light_rays(cl2_renderer* r) { STAGE_CALL_PROLOGUE(r); TRY(launch_subpaths(r, r->stream, r->sets[r->cur], 1)); return drain(r); }
+int cl2_trace_camera_rays(cl2_renderer* r) { STAGE_CALL_PROLOGUE(r); TRY(launch_subpaths(r, r->stream, r->sets[r->cur], 2)); return drain(r); }
 int cl2_join_paths(cl2_renderer* r) {
-    STAGE_PROLOGUE(r);
+    STAGE_CALL_PROLOGUE(r);
     TRY(launch_connect(r, r->stream, r->sets[r->cur], 0));
     TRY(launch_resolve(r, r->stream, r->sets[r->cur], 0));
     return drain(r);
 }
-int cl2_finalize_samples(cl2_renderer* r) { STAGE_PROLOGUE(r); TRY(launch_finalize(r, r->stream)); return drain(r); }
+int cl2_finalize_samples(cl2_renderer* r) { STAGE_CALL_PROLOGUE(r); TRY(launch_finalize(r, r->stream)); return drain(r); }
 /* The t=1 splats were added to the light image by join_paths (float atomics); nothing is left of the
  * reference's sort + bincount + gather (src/renderer.py:212-250) but a synchronisation point. */
-int cl2_gather_light_image(cl2_renderer* r) { STAGE_PROLOGUE(r); return drain(r); }
+int cl2_gather_light_image(cl2_renderer* r) { STAGE_CALL_PROLOGUE(r); return drain(r); }
 int cl2_process_images(cl2_renderer* r) {
-    STAGE_PROLOGUE(r);
+    STAGE_CALL_PROLOGUE(r);
     TRY(launch_accumulate(r, r->stream));
     r->samples += (uint64_t)r->streams;
+    r->cam_uniform += (uint64_t)r->streams;
     return drain(r);
 }
 
@@ -1076,8 +1121,16 @@ int subpath_ray_tally(cl2_renderer* r, unsigned long long* out) {
 // the current one); ends with everything complete and `cur` = the set of the last sample.
 // `steady`: r->tune_period_ms = the time from the end of the first sample to the end of the last one, per sample -- what a long run
 // costs per sample, without the fill of the pipeline (the first sample's subpath stage has nothing beside it).
+int ensure_maps(cl2_renderer* r) {
+    for (int q = 0; q < 3; q++)
+        if (!r->d_map[q]) TRY(dev_alloc(r, &r->d_map[q], (size_t)r->B));
+    return CL2_OK;
+}
+
 int run_chunk(cl2_renderer* r, bool pipe, int count, bool steady = false) {
     const int first_set = r->cur;
+    const bool mapped = r->density;           // adaptive sampling: every pass writes its set's slot map first (adaptive.hpp)
+    if (mapped) TRY(ensure_maps(r));
     r->pipe_active = pipe;
     for (int i = 0; i < count; i++) {
         const int ps = pipe ? (first_set + i) % 3 : r->cur, cs = pipe ? (i & 1) : 0;
@@ -1086,7 +1139,16 @@ int run_chunk(cl2_renderer* r, bool pipe, int count, bool steady = false) {
         hipStream_t s_res = pipe ? (pipeline_stages(r) == 2 ? r->stream_res : r->stream_conn) : r->stream;
         // resolve of sample i-3 was the last reader of this subpath set
         if (pipe && i >= 3) HIP_TRY(r, hipStreamWaitEvent(r->stream, r->ev_res[(i - 3) % 6], 0));
-        TRY(launch_generate_both(r, r->stream, set));
+        // (the map belongs to the subpath set: the same event orders its reuse)
+        const int* map = mapped ? r->d_map[ps] : nullptr;
+        const uint32_t pass = mapped ? r->dens_pass++ : 0u;
+        if (mapped) {
+            Timed t(r, ST_GENERATE, r->stream);
+            hipLaunchKernelGGL(k_dens_expand, dim3(grid_for(r->B)), dim3(BLOCK), 0, r->stream, r->B, r->FB, (const uint64_t*)r->d_dens_C,
+                               pass, r->d_map[ps]);
+            HIP_TRY(r, hipGetLastError());
+        }
+        TRY(launch_generate_both(r, r->stream, set, map));
         TRY(launch_subpaths(r, r->stream, set, 3));
         if (pipe) {
             HIP_TRY(r, hipEventRecord(r->ev_paths[i % 3], r->stream));
@@ -1099,11 +1161,12 @@ int run_chunk(cl2_renderer* r, bool pipe, int count, bool steady = false) {
             HIP_TRY(r, hipEventRecord(r->ev_conn[i & 1], s_conn));
             HIP_TRY(r, hipStreamWaitEvent(s_res, r->ev_conn[i & 1], 0));
         }
-        TRY(launch_resolve(r, s_res, set, cs));
-        TRY(launch_finalize_accumulate(r, s_res));
+        TRY(launch_resolve(r, s_res, set, cs, map));
+        TRY(launch_finalize_accumulate(r, s_res, mapped, pass));
         if (steady && count >= 2 && (i == 0 || i == count - 1)) HIP_TRY(r, hipEventRecord(r->ev_tune[i == 0 ? 0 : 1], s_res));
         if (pipe) HIP_TRY(r, hipEventRecord(r->ev_res[i % 6], s_res));
         r->samples += (uint64_t)r->streams;
+        if (!mapped) r->cam_uniform += (uint64_t)r->streams;
         // bound the number of in-flight event pairs while profiling
         if (r->profiling && r->spans.size() > 4096) TRY(drain(r));
     }
@@ -1238,6 +1301,8 @@ int cl2_reset_accumulators(cl2_renderer* r) {
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     HIP_TRY(r, hipMemset(r->d_acc, 0, 8 * (size_t)r->FB * sizeof(float)));
     if (r->d_mom) HIP_TRY(r, hipMemset(r->d_mom, 0, 8 * (size_t)r->FB * sizeof(float)));
+    if (r->d_cam_count) HIP_TRY(r, hipMemset(r->d_cam_count, 0, (size_t)r->FB * sizeof(unsigned)));
+    r->cam_uniform = 0;
     r->mom_valid = r->d_mom != nullptr;
     r->acc_clean = true;
     r->samples = 0;
@@ -1344,6 +1409,7 @@ int cl2_comm_init_rank(cl2_renderer* r, int nranks, int rank, const void* unique
     if (!unique_id || n_bytes != sizeof(ncclUniqueId)) return fail(r, CL2_E_INVALID, "unique id must be cl2_comm_unique_id_bytes() long");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(r, CL2_E_INVALID, "need 0 <= rank < nranks");
     if (r->comm) return fail(r, CL2_E_STATE, "this renderer already has a communicator (cl2_comm_destroy first)");
+    if (r->density || r->adaptive) return fail(r, CL2_E_STATE, "adaptive sampling is per handle: cl2_set_sample_density(NULL) and cl2_set_adaptive_sampling(0) first");
     std::string why;
     RcclApi* api = rccl_api(why);
     if (!api) return fail(r, CL2_E_COMM, why);
@@ -1995,6 +2061,92 @@ int eval_rel_error(cl2_renderer* r, double floor, double* out) {
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     return CL2_OK;
 }
+
+// ---- adaptive sampling (adaptive.hpp) ----
+int ensure_density_buffers(cl2_renderer* r) {
+    const size_t FB = (size_t)r->FB;
+    if (!r->d_cam_count) {                                   // kept for the life of the handle: counts survive a NULL density
+        TRY(dev_alloc(r, &r->d_cam_count, FB));
+        HIP_TRY(r, hipMemset(r->d_cam_count, 0, FB * sizeof(unsigned)));
+    }
+    if (r->d_dens_tmp) return CL2_OK;                        // the last thing set up (see ensure_det_buffers)
+    dev_free(r, r->d_dens_C); dev_free(r, r->d_dens_M); dev_free(r, r->d_dens_invm); dev_free(r, r->d_dens_m);
+    dev_free(r, r->d_dens_partial); dev_free(r, r->d_dens_fsum);
+    TRY(dev_alloc(r, &r->d_dens_C, FB));
+    TRY(dev_alloc(r, &r->d_dens_M, FB));
+    TRY(dev_alloc(r, &r->d_dens_invm, FB));
+    TRY(dev_alloc(r, &r->d_dens_m, FB));
+    TRY(dev_alloc(r, &r->d_dens_partial, (size_t)3 * DENS_BLOCKS + 3));
+    TRY(dev_alloc(r, &r->d_dens_fsum, (size_t)1));
+    size_t bytes = 0;
+    HIP_TRY(r, dens_scan(nullptr, bytes, r->d_dens_M, r->d_dens_C, FB, r->stream));
+    unsigned char* tmp = nullptr;
+    TRY(dev_alloc(r, &tmp, bytes));
+    r->d_dens_tmp = tmp; r->dens_tmp_bytes = bytes;
+    return CL2_OK;
+}
+
+void free_density(cl2_renderer* r) {
+    dev_free(r, r->d_dens_C); dev_free(r, r->d_dens_M); dev_free(r, r->d_dens_invm); dev_free(r, r->d_dens_m);
+    dev_free(r, r->d_dens_partial); dev_free(r, r->d_dens_fsum);
+    unsigned char* tmp = static_cast<unsigned char*>(r->d_dens_tmp);
+    dev_free(r, tmp);
+    r->d_dens_tmp = nullptr; r->dens_tmp_bytes = 0;
+    for (int q = 0; q < 3; q++) dev_free(r, r->d_map[q]);
+    r->density = false;
+}
+
+// d_dens_m holds W*H positive finite weights: normalise to mean 1, quantise (M, sum M = W*H 2^16), 1/m and the prefix sum C
+int dens_quantise(cl2_renderer* r) {
+    const int FB = r->FB;
+    hipStream_t st = r->stream;
+    const int grid = std::min((FB + 255) / 256, DENS_BLOCKS);
+    double* tot = r->d_dens_partial + 3 * DENS_BLOCKS;
+    hipLaunchKernelGGL(k_dens_sum, dim3(grid), dim3(256), 0, st, FB, (const float*)r->d_dens_m, r->d_dens_partial);
+    hipLaunchKernelGGL(k_dens_final, dim3(1), dim3(256), 0, st, (const double*)r->d_dens_partial, grid, tot);
+    HIP_TRY(r, hipMemsetAsync(r->d_dens_fsum, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_dens_floor, dim3((FB + 255) / 256), dim3(256), 0, st, FB, (const float*)r->d_dens_m, (const double*)tot,
+                       r->d_dens_M, r->d_dens_fsum);
+    HIP_TRY(r, hipGetLastError());
+    unsigned long long fsum = 0;
+    HIP_TRY(r, hipMemcpyAsync(&fsum, r->d_dens_fsum, sizeof fsum, hipMemcpyDeviceToHost, st));
+    HIP_TRY(r, hipStreamSynchronize(st));
+    const uint64_t target = (uint64_t)FB * 65535u;
+    if (fsum > target) { r->density = false; return fail(r, CL2_E_STATE, "density quantisation: the floors exceed the frame's units"); }
+    hipLaunchKernelGGL(k_dens_finish, dim3((FB + 255) / 256), dim3(256), 0, st, FB, (uint64_t)(target - fsum), r->d_dens_M, r->d_dens_invm);
+    HIP_TRY(r, hipGetLastError());
+    size_t bytes = r->dens_tmp_bytes;
+    HIP_TRY(r, dens_scan(r->d_dens_tmp, bytes, r->d_dens_M, r->d_dens_C, (size_t)FB, st));
+    uint64_t last = 0;
+    HIP_TRY(r, hipMemcpyAsync(&last, r->d_dens_C + (FB - 1), sizeof last, hipMemcpyDeviceToHost, st));
+    HIP_TRY(r, hipStreamSynchronize(st));
+    if (last != ((uint64_t)FB << DENS_SHIFT)) { r->density = false; return fail(r, CL2_E_STATE, "density quantisation: the units do not add up"); }
+    r->density = true;
+    return CL2_OK;
+}
+
+int dens_update(cl2_renderer* r, double floor, double share) {
+    TRY(ensure_density_buffers(r));
+    hipStream_t st = r->stream;
+    const int grid = std::min((r->FB + 255) / 256, DENS_BLOCKS);
+    double* tot = r->d_dens_partial + 3 * DENS_BLOCKS;
+    hipLaunchKernelGGL(k_dens_terms, dim3(grid), dim3(256), 0, st, r->FB, (const float*)r->d_acc, (const float*)r->d_mom, floor,
+                       r->d_dens_m, r->d_dens_partial);
+    hipLaunchKernelGGL(k_dens_final, dim3(1), dim3(256), 0, st, (const double*)r->d_dens_partial, grid, tot);
+    HIP_TRY(r, hipGetLastError());
+    double h[3] = {0, 0, 0};
+    HIP_TRY(r, hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(r, hipStreamSynchronize(st));
+    if (!(h[1] > 0.0)) return fail(r, CL2_E_STATE, "no pixel has a finite error term (fewer than two samples everywhere)");
+    hipLaunchKernelGGL(k_dens_from_terms, dim3((r->FB + 255) / 256), dim3(256), 0, st, r->FB, (const double*)tot, share, r->d_dens_m);
+    HIP_TRY(r, hipGetLastError());
+    return dens_quantise(r);
+}
+
+int no_comm(cl2_renderer* r) {
+    if (r->comm) return fail(r, CL2_E_STATE, "adaptive sampling is per handle: not on a handle with a communicator");
+    return CL2_OK;
+}
 }  // namespace
 
 int cl2_set_error_tracking(cl2_renderer* r, int on) {
@@ -2072,8 +2224,11 @@ int cl2_run_until(cl2_renderer* r, double target, double floor, int min_passes, 
     if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
     if (check_every < 1) return fail(r, CL2_E_INVALID, "check_every must be >= 1");
     if (max_passes < 1 || min_passes < 0 || min_passes > max_passes) return fail(r, CL2_E_INVALID, "need 0 <= min_passes <= max_passes, max_passes >= 1");
+    if (r->adaptive && (long long)min_passes * r->streams < 2)
+        return fail(r, CL2_E_INVALID, "adaptive sampling needs two addends per pixel before its first update: min_passes * streams >= 2");
     STAGE_PROLOGUE(r);
     TRY(need_moments(r));
+    if (r->adaptive) TRY(no_comm(r));
     int done = 0;
     double e = std::numeric_limits<double>::infinity();
     bool evaluated = false;
@@ -2084,6 +2239,7 @@ int cl2_run_until(cl2_renderer* r, double target, double floor, int min_passes, 
     }
     while (done < max_passes) {
         const int chunk = std::min(check_every, max_passes - done);
+        if (r->adaptive) TRY(dens_update(r, floor, r->adaptive_share));
         TRY(cl2_run_samples(r, chunk));
         done += chunk;
         if (passes_done) *passes_done = done;
@@ -2093,6 +2249,68 @@ int cl2_run_until(cl2_renderer* r, double target, double floor, int min_passes, 
     }
     if (!evaluated) TRY(eval_rel_error(r, floor, &e));
     if (error_out) *error_out = e;
+    return CL2_OK;
+}
+
+// ---------------------------------------------------------------- adaptive sampling (csrc/adaptive.hpp)
+int cl2_set_sample_density(cl2_renderer* r, const float* density, size_t n) {
+    if (!r) return CL2_E_INVALID;
+    TRY(no_comm(r));
+    if (density) {
+        if (n != (size_t)r->FB) return fail(r, CL2_E_INVALID, "the density holds W*H weights");
+        for (size_t i = 0; i < n; i++)
+            if (!(density[i] > 0.0f) || !std::isfinite(density[i])) return fail(r, CL2_E_INVALID, "density weights must be positive and finite");
+    }
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    if (!density) { free_density(r); return CL2_OK; }
+    TRY(ensure_density_buffers(r));
+    HIP_TRY(r, hipMemcpy(r->d_dens_m, density, n * sizeof(float), hipMemcpyHostToDevice));
+    return dens_quantise(r);
+}
+
+int cl2_read_sample_density(cl2_renderer* r, float* out, size_t n) {
+    if (!r || !out) return CL2_E_INVALID;
+    if (n != (size_t)r->FB) return fail(r, CL2_E_INVALID, "the density holds W*H weights");
+    if (!r->density) { for (size_t i = 0; i < n; i++) out[i] = 1.0f; return CL2_OK; }
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    std::vector<uint64_t> c(n);
+    HIP_TRY(r, hipMemcpy(c.data(), r->d_dens_C, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) out[i] = (float)((double)(c[i] - (i ? c[i - 1] : 0)) / 65536.0);
+    return CL2_OK;
+}
+
+int cl2_update_sample_density(cl2_renderer* r, double floor, double uniform_share) {
+    if (!r) return CL2_E_INVALID;
+    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
+    if (!(uniform_share > 0.0 && uniform_share <= 1.0)) return fail(r, CL2_E_INVALID, "uniform_share must be in (0, 1]");
+    TRY(no_comm(r));
+    TRY(need_moments(r));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    return dens_update(r, floor, uniform_share);
+}
+
+int cl2_set_adaptive_sampling(cl2_renderer* r, int on, double uniform_share) {
+    if (!r) return CL2_E_INVALID;
+    if (on != 0 && on != 1) return fail(r, CL2_E_INVALID, "adaptive sampling: 0 off, 1 on");
+    if (on && !(uniform_share > 0.0 && uniform_share <= 1.0)) return fail(r, CL2_E_INVALID, "uniform_share must be in (0, 1]");
+    if (on) TRY(no_comm(r));
+    r->adaptive = on != 0;
+    if (on) r->adaptive_share = uniform_share;
+    return CL2_OK;
+}
+int cl2_get_adaptive_sampling(const cl2_renderer* r) { return r ? (r->adaptive ? 1 : 0) : CL2_E_INVALID; }
+
+int cl2_read_camera_samples(cl2_renderer* r, float* out, size_t n) {
+    if (!r || !out) return CL2_E_INVALID;
+    if (n != (size_t)r->FB) return fail(r, CL2_E_INVALID, "the camera sample counts hold W*H entries");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    std::vector<unsigned> c(n, 0u);
+    if (r->d_cam_count) HIP_TRY(r, hipMemcpy(c.data(), r->d_cam_count, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) out[i] = (float)((uint64_t)c[i] + r->cam_uniform);
     return CL2_OK;
 }
 

@@ -16,7 +16,7 @@ import time
 import numpy as np
 
 from .distributed import rank_info
-from .renderer import ERROR_FLOOR, Renderer, RendererError
+from .renderer import ERROR_FLOOR, UNIFORM_SHARE, Renderer, RendererError
 from .scene import create_scene_from_preset_with_params
 
 
@@ -52,6 +52,11 @@ def main(argv=None):
     ap.add_argument("--error-floor", type=float, default=None,
                     help=f"floor of the relative error's denominator L + floor (default {ERROR_FLOOR})")
     ap.add_argument("--check-every", type=int, default=8, help="passes between two checks of --target-error")
+    ap.add_argument("--adaptive", action="store_true",
+                    help="with --target-error: spread the camera samples by the per-pixel error estimate before every check "
+                         "(adaptive sampling, DESIGN.md 6.5)")
+    ap.add_argument("--uniform-share", type=float, default=None,
+                    help=f"share of the density that stays uniform under --adaptive, in (0, 1] (default {UNIFORM_SHARE})")
     args = ap.parse_args(argv)
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
         ap.error("--target-error must be positive and finite")
@@ -59,6 +64,10 @@ def main(argv=None):
         ap.error("--error-floor must be >= 0 and finite")
     if args.check_every < 1:
         ap.error("--check-every must be >= 1")
+    if args.adaptive and args.target_error is None:
+        ap.error("--adaptive needs --target-error")
+    if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
+        ap.error("--uniform-share must be in (0, 1]")
 
     rank, local_rank, world = rank_info()
     out_dir = os.path.join(args.out_root, args.movie_name)
@@ -79,7 +88,8 @@ def main(argv=None):
             renderer = Renderer(scene, device=0)     # the launcher exposes one GPU per rank: it is device 0
         note = ""
         if args.target_error is not None:
-            _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every)
+            _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every,
+                                               adaptive=args.adaptive, uniform_share=args.uniform_share)
             note = f" ({renderer.samples} samples, relative error {reached:.4g})"
         else:
             renderer.run_samples(args.samples)

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _native
 from .distributed import rank_info, samples_for_rank, join_communicator
-from .renderer import ERROR_FLOOR, Renderer, RendererError, stream_seeds
+from .renderer import ERROR_FLOOR, UNIFORM_SHARE, Renderer, RendererError, stream_seeds
 from .scene import create_scene_from_preset
 
 
@@ -48,6 +48,11 @@ def main(argv=None):
     ap.add_argument("--error-floor", type=float, default=None,
                     help=f"floor of the relative error's denominator L + floor (default {ERROR_FLOOR})")
     ap.add_argument("--check-every", type=int, default=8, help="passes between two checks of --target-error")
+    ap.add_argument("--adaptive", action="store_true",
+                    help="with --target-error: spread the camera samples by the per-pixel error estimate before every check "
+                         "(adaptive sampling, DESIGN.md 6.5)")
+    ap.add_argument("--uniform-share", type=float, default=None,
+                    help=f"share of the density that stays uniform under --adaptive, in (0, 1] (default {UNIFORM_SHARE})")
     ap.add_argument("--error-out", type=str, default=None,
                     help="save the per-pixel standard error (Renderer.standard_error: (H, W, 4) float32 b, g, r, luma) as .npy")
     args = ap.parse_args(argv)
@@ -58,6 +63,10 @@ def main(argv=None):
         ap.error("--error-floor must be >= 0 and finite")
     if args.check_every < 1:
         ap.error("--check-every must be >= 1")
+    if args.adaptive and args.target_error is None:
+        ap.error("--adaptive needs --target-error")
+    if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
+        ap.error("--uniform-share must be in (0, 1]")
 
     rank, local_rank, world = rank_info()
     if args.target_error is not None and world > 1:
@@ -84,7 +93,8 @@ def main(argv=None):
     try:
         if args.target_error is not None:
             _, reached = renderer.render_until(args.target_error, max(1, -(-args.samples // K)), floor=args.error_floor,
-                                               check_every=args.check_every)
+                                               check_every=args.check_every, adaptive=args.adaptive,
+                                               uniform_share=args.uniform_share)
         else:
             renderer.run_samples(-(-samples_for_rank(args.samples, rank, world) // K))
     except (KeyboardInterrupt, RendererError) as e:

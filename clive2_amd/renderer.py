@@ -32,6 +32,10 @@ LIGHT, CAMERA = 0, 1
 # leaves it a relative error everywhere else
 ERROR_FLOOR = 0.001
 
+# Default uniform share beta of adaptive sampling's density m = beta + (1 - beta) r / mean(r) (Renderer.update_sample_density,
+# DESIGN.md 6.5)
+UNIFORM_SHARE = 0.25
+
 
 def make_seeds(batch_size, seed=20240928, rank=0):
     """Seed buffer of SURVEY.md §8(d): `RandomState(seed+rank).randint(0, 2**32, (B,2), uint32)`
@@ -527,20 +531,72 @@ class Renderer:
         self._check(self._L.cl2_relative_error(self._h, f, C.byref(e)), "cl2_relative_error")
         return e.value
 
-    def render_until(self, target, max_samples, floor=None, min_samples=2, check_every=8):
+    def render_until(self, target, max_samples, floor=None, min_samples=2, check_every=8, adaptive=False, uniform_share=None):
         """Render until relative_error(floor) <= target, at most `max_samples` passes (units of run_samples: a pass renders
         one sample per stream): first `min_samples`, then chunks of `check_every`, checking after each.  Turns error tracking on
-        if it is off.  Returns (passes rendered, error reached)."""
+        if it is off.  adaptive=True: before every chunk the sample density is rebuilt from the error estimate
+        (update_sample_density(floor, uniform_share)); the density stays set afterwards.  Returns (passes rendered, error reached)."""
+        share = self._uniform_share(uniform_share)
+        if adaptive and int(min_samples) * self.streams < 2:
+            raise ValueError("adaptive sampling needs two samples per pixel before its first update: min_samples * streams >= 2")
         if not self.error_tracking:
             self.set_error_tracking(True)
         f = self.ERROR_FLOOR if floor is None else float(floor)
         done, e = C.c_int(0), C.c_double(0.0)
+        self._check(self._L.cl2_set_adaptive_sampling(self._h, int(bool(adaptive)), share), "cl2_set_adaptive_sampling")
         try:
             self._check(self._L.cl2_run_until(self._h, float(target), f, int(min_samples), int(max_samples), int(check_every),
                                               C.byref(done), C.byref(e)), "cl2_run_until")
         finally:
             self.samples += done.value * self.streams
+            if adaptive:
+                self._L.cl2_set_adaptive_sampling(self._h, 0, share)
         return done.value, e.value
+
+    # ---- adaptive sampling (cl2_set_sample_density ... cl2_read_camera_samples, csrc/adaptive.hpp, DESIGN.md 6.5) ----
+    UNIFORM_SHARE = UNIFORM_SHARE
+
+    def _uniform_share(self, uniform_share):
+        share = self.UNIFORM_SHARE if uniform_share is None else float(uniform_share)
+        if not (0.0 < share <= 1.0):
+            raise ValueError("uniform_share must be in (0, 1]")
+        return share
+
+    def set_sample_density(self, density):
+        """Spread each pass's camera samples over the pixels by `density` ((H, W) or W*H positive finite weights, normalised to
+        mean 1): pixel q gets floor(m_q) or ceil(m_q) camera samples per pass and stream, each weighted 1/m_q, so the expected
+        picture is the uniform one.  None = uniform (the default kernels).  Only run_samples / render_until render with a
+        density; the stage methods refuse."""
+        if density is None:
+            self._check(self._L.cl2_set_sample_density(self._h, None, C.c_size_t(0)), "cl2_set_sample_density")
+            return
+        d = np.ascontiguousarray(density, dtype=np.float32).reshape(-1)
+        if d.size != self.batch_size:
+            raise ValueError(f"density must hold W*H = {self.batch_size} weights, got {d.size}")
+        if not (np.all(np.isfinite(d)) and np.all(d > 0)):
+            raise ValueError("density weights must be positive and finite")
+        self._check(self._L.cl2_set_sample_density(self._h, ptr(d), C.c_size_t(d.size)), "cl2_set_sample_density")
+
+    def sample_density(self):
+        """The quantised density in use, float32 (H, W), mean 1 (units of 2^-16); all ones without one."""
+        out = np.empty((self.pixel_height, self.pixel_width), np.float32)
+        self._check(self._L.cl2_read_sample_density(self._h, ptr(out), C.c_size_t(out.size)), "cl2_read_sample_density")
+        return out
+
+    def update_sample_density(self, floor=None, uniform_share=None):
+        """Set the density from the error estimate: m = beta + (1 - beta) r / mean(r), r = each pixel's term
+        sqrt(var_L) / (L + floor) of relative_error(floor), clipped to 16 mean(r); beta = uniform_share (default UNIFORM_SHARE)."""
+        share = self._uniform_share(uniform_share)
+        f = self.ERROR_FLOOR if floor is None else float(floor)
+        if not (f >= 0.0 and np.isfinite(f)):
+            raise ValueError("floor must be >= 0 and finite")
+        self._check(self._L.cl2_update_sample_density(self._h, f, share), "cl2_update_sample_density")
+
+    def camera_samples(self):
+        """Camera samples each pixel received since reset_accumulators(), float32 (H, W)."""
+        out = np.empty((self.pixel_height, self.pixel_width), np.float32)
+        self._check(self._L.cl2_read_camera_samples(self._h, ptr(out), C.c_size_t(out.size)), "cl2_read_camera_samples")
+        return out
 
     def probe_math(self, which, x):
         """Device detmath / exact-reciprocal functions on a float32 array (`which`: sin cos acos atan exp asin rcp div_pi)."""

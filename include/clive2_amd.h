@@ -435,6 +435,34 @@ int cl2_relative_error(cl2_renderer* r, double floor, double* out);
 int cl2_run_until(cl2_renderer* r, double target, double floor, int min_passes, int max_passes, int check_every, int* passes_done,
                   double* error_out);
 
+/* Adaptive sampling (clive2_amd/csrc/adaptive.hpp).  A density m (W*H positive weights, normalised to mean 1 and
+ * quantised to units of 2^-16) spreads each sample stream's W*H camera slots over the pixels: pixel q gets floor(m_q) or
+ * ceil(m_q) of them per pass and stream, E = m_q, contiguous and in raster order, and each of its camera samples enters the
+ * picture with the factor 1/m_q -- so the expected picture is the uniform one.  The light image, acc row 7 (one addend per pixel
+ * and stream) and the moments keep their meaning.  Only cl2_run_samples / cl2_tune / cl2_run_until render with a density; one
+ * rank only.
+ *   - density NULL: uniform, the default kernels byte for byte.  Any density set explicitly, a flat one included, runs the
+ *     mapped kernels.  CL2_E_INVALID for a NaN, +-inf or <= 0 weight or n != W*H.
+ *   - While a density is set the stage calls cl2_make_light_rays ... cl2_process_images and the test variant's cross-check
+ *     resolve (debug bits 4-6 = 7) return CL2_E_STATE.
+ *   - Every density call returns CL2_E_STATE on a handle with a communicator, and cl2_comm_init_rank refuses a handle with a
+ *     density or adaptive sampling on.
+ *   - cl2_upload_scene keeps the density (it describes pixels, not the scene); cl2_set_sample_streams keeps it and re-allocates
+ *     the slot maps with the other per-stream state. */
+int cl2_set_sample_density(cl2_renderer* r, const float* density, size_t n);
+/* the quantised density in use (M_q / 2^16 rounded to float: exact below 256); 1.0 everywhere without one */
+int cl2_read_sample_density(cl2_renderer* r, float* out, size_t n);
+/* Density from the error estimate: r_q = sqrt(var_L) / (L + floor) per pixel (0 uncovered; +inf with fewer than two addends),
+ * clipped to 16 mean(r) (mean over the finite terms), m_q = uniform_share + (1 - uniform_share) r_q / mean(r).  CL2_E_STATE while
+ * the moments are invalid (cl2_read_standard_error's rule) or when no term is finite.  floor >= 0, uniform_share in (0, 1]. */
+int cl2_update_sample_density(cl2_renderer* r, double floor, double uniform_share);
+/* on: cl2_run_until calls cl2_update_sample_density(floor, uniform_share) after min_passes and before every chunk; it then needs
+ * min_passes * streams >= 2 (else CL2_E_INVALID).  Off (the default): cl2_run_until is unchanged. */
+int cl2_set_adaptive_sampling(cl2_renderer* r, int on, double uniform_share);
+int cl2_get_adaptive_sampling(const cl2_renderer* r);
+/* camera samples each pixel received since the last cl2_reset_accumulators (one per stream and pass without a density) */
+int cl2_read_camera_samples(cl2_renderer* r, float* out, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COUNTERS = ("SQ_INSTS_VALU", "TCP_TOTAL_CACHE_ACCESSES_sum")
 # r08: the accumulate kernels became templates on MOMENTS; the render runs the <false> instantiations
-RENAMED = {"k_finalize_accumulate": "k_finalize_accumulate<false>", "k_accumulate": "k_accumulate<false>"}
+# r11: the camera-ray generator and the resolve kernel gained a MAPPED parameter (adaptive sampling); the render runs <false>
+RENAMED = {"k_finalize_accumulate": "k_finalize_accumulate<false>", "k_accumulate": "k_accumulate<false>",
+           "k_gen_rays": "k_gen_rays<false>", "k_gen_camera_rays": "k_gen_camera_rays<false>",
+           **{f"k_connect_resolve<{a}>": f"k_connect_resolve<{a},false>"
+              for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true")}}
 
 
 def kernels(tag, workload):
