@@ -2,12 +2,13 @@
 quantisation to units of 2^-16, the per-pass slot offsets and slot ranges, the weights 1/m and the mapped finalize + accumulate
 in float32, every operation in the order the kernels perform it.
 
-The one step that is not bit-exact with the device is the double sum of the density in `quantise` (the device sums over a
-fixed grid of workgroups, numpy pairwise): the scale of the floors can then differ in its last bits, and an M_q by a unit.  Tests
-that compare with the device take M from Renderer.sample_density() and restate everything after it exactly."""
+The two double sums (the finite error terms in `density_from_terms`, the density in `quantise`) are taken in the device's
+reduction order (error_reference.grid_sum), so M of a density and of an error state equals the device's as integers; GPU tests
+assert that on injected accumulator / moment states at 7 x 5 ... 1920 x 1080 (tests/test_gpu_adaptive.py).  order="pairwise"
+gives numpy's own sum instead: the scale of the floors can then differ in its last bits, and an M_q by a unit."""
 import numpy as np
 
-from error_reference import scrub, add_moments, variances
+from error_reference import scrub, add_moments, variances, grid_sum
 
 F = np.float32
 SHIFT = 16
@@ -32,14 +33,14 @@ def offset(pass_index, s):
     return fmix32((0x9E3779B9 * pass_index + s) & M32) >> 16
 
 
-def quantise(m):
+def quantise(m, order="grid"):
     """M (uint64) of a density m (positive finite weights): M_q = 1 + F_q + extra_q (one unit reserved per pixel: M_q >= 1),
     F_q = floor(m_q scale),
     scale = FB (2^16 - 1) / sum m (1 - 2^-30), the deficit D = FB (2^16 - 1) - sum F spread as
     extra_q = floor((q+1) D / FB) - floor(q D / FB).  sum M = FB 2^16 exactly."""
     m = np.asarray(m, F).reshape(-1).astype(np.float64)
     FB = m.size
-    scale = (FB * 65535.0 / np.sum(m)) * (1.0 - 2.0 ** -30)
+    scale = (FB * 65535.0 / (grid_sum(m) if order == "grid" else np.sum(m))) * (1.0 - 2.0 ** -30)
     Fq = np.floor(m * scale).astype(np.uint64)
     D = FB * 65535 - int(Fq.sum(dtype=np.uint64))
     assert D >= 0
@@ -61,7 +62,7 @@ def prefix(M):
 
 
 def ranges(C, u):
-    """slots [lo, hi) of every pixel in a plane drawn with offset u"""
+    """slots [lo, hi) of every pixel in a plane drawn with offset u (C in 64 bits: it passes 2^32 from 65,536 pixels on)"""
     C = np.asarray(C, np.uint64)
     prev = np.concatenate([np.zeros(1, np.uint64), C[:-1]])
     lo = ((prev + np.uint64(u)) >> np.uint64(SHIFT)).astype(np.int64)
@@ -99,35 +100,40 @@ def terms(acc, mom, floor):
     t = np.where(state == 2, np.where(vl > 0, t, 0.0), 0.0)
     t = np.where((state == 2) & (vl > 0) & ~((t >= 0) & (t < np.inf)), np.inf, t)
     t = np.where(state == 1, np.inf, t)
-    return t.astype(F)
+    with np.errstate(over="ignore"):
+        return t.astype(F)                            # +inf where the term exceeds float32: clipped like the others
 
 
-def density_from_terms(r, beta):
-    """m = beta + (1 - beta) min(r, KAPPA mean) / mean in float32, mean over the finite terms; None when none is finite"""
-    r = np.asarray(r, F)
+def density_from_terms(r, beta, order="grid"):
+    """m = beta + (1 - beta) min(r, KAPPA mean) / mean in float32, mean over the finite terms (their float32 values widened, summed
+    in the device's order or, order="pairwise", numpy's); None when none is finite"""
+    r = np.asarray(r, F).reshape(-1)
     fin = np.isfinite(r)
     if not fin.any():
         return None
-    mean = np.sum(r[fin].astype(np.float64)) / fin.sum()
+    total = grid_sum(np.where(fin, r, F(0))) if order == "grid" else np.sum(r[fin].astype(np.float64))
+    mean = total / fin.sum()
     if not mean > 0:
         return np.ones(r.shape, F)
     t = np.minimum(np.where(fin, r.astype(np.float64), np.inf), KAPPA * mean)
     return (beta + (1.0 - beta) * (t / mean)).astype(F)
 
 
-def finalize_accumulate(agg, light, uni, acc, mom, C, invm, pass_index, W, H, streams=1):
+def finalize_accumulate(agg, light, uni, acc, mom, C, invm, pass_index, W, H, streams=1, pixels=None):
     """k_finalize_accumulate_mapped on host arrays: agg [13][B] (rows of export_aggregators' layout: 9 filter weights,
     contribution b, g, r, weight), light / uni (B, 4), acc / mom [8][FB] (updated in place, mom may be None).  Returns the
-    camera samples each pixel received."""
+    camera samples each pixel received.  pixels = an index array: only those pixels are restated (the per-pixel loops are
+    Python); the columns of acc / mom of every other pixel then hold no restatement and must not be compared."""
     FB = W * H
     B = FB * streams
     received = np.zeros(FB, np.int64)
+    todo = range(FB) if pixels is None else [int(p) for p in pixels]
     for s in range(streams):
         base = s * FB
         lo, hi = ranges(C, offset(pass_index, s))
         tot = np.zeros((FB, 3), F)
         wsum = np.zeros(FB, F)
-        for p in range(FB):
+        for p in todo:
             t0 = t1 = t2 = F(0)
             ws = F(0)
             px, py = p % W, p // W
@@ -154,7 +160,7 @@ def finalize_accumulate(agg, light, uni, acc, mom, C, invm, pass_index, W, H, st
         for c in range(3):
             acc[c] = (acc[c] + x[:, c]).astype(F)
         acc[3] = (acc[3] + w).astype(F)
-        for p in range(FB):
+        for p in todo:
             for slot in range(lo[p], hi[p]):
                 u4 = scrub(uni[base + slot, :3])
                 for c in range(3):

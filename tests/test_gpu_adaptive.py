@@ -1,7 +1,11 @@
 """Adaptive sampling on the device (csrc/adaptive.hpp): a flat density through the mapped kernels gives the
 default path's bytes; a non-uniform density's camera sample counts and one pass's accumulators equal their numpy restatement
 (tests/adaptive_reference.py); an uneven density leaves the picture's expectation unchanged; render_until(adaptive=True)
-against the uniform render; the refusals and the command line."""
+against the uniform render; the refusals and the command line.
+
+The density from the error estimate (k_dens_terms, k_dens_final, k_dens_from_terms and the quantisation) is compared with the
+restatement as integers on injected states (tests/error_states.py) at frames up to 1920 x 1080, and mapped passes run at
+320 x 240 and 1920 x 1080, where the prefix sum C of the quantised density no longer fits 32 bits."""
 import os
 import subprocess
 import sys
@@ -10,6 +14,8 @@ import numpy as np
 import pytest
 
 import adaptive_reference as ar
+import error_reference as er
+import error_states as es
 from test_gpu_denoise import _cornell, _glass, _open_scene
 
 pytestmark = pytest.mark.gpu
@@ -77,8 +83,8 @@ def test_camera_samples_equal_the_numpy_expansion():
     r.set_sample_density(_fixed_density(64, 48))
     M = ar.from_density(r.sample_density())
     assert int(M.sum()) == 64 * 48 * ar.UNIT
-    # the device's quantisation of the same weights, restated (the double sum may move a unit: DESIGN 6.5)
-    assert np.abs(M.astype(np.int64) - ar.quantise(_fixed_density(64, 48)).astype(np.int64)).max() <= 1
+    # the device's quantisation of the same weights, restated with the double sum in the device's order
+    assert np.array_equal(M, ar.quantise(_fixed_density(64, 48)))
     r.run_samples(7)                               # pass numbers 0..6 of this handle, the level probe's pass included
     want = ar.camera_samples(ar.prefix(M), 0, 7, K)
     assert np.array_equal(r.camera_samples().reshape(-1), want.astype(np.float32))
@@ -242,3 +248,193 @@ def test_cli_adaptive_writes_a_png(tmp_path):
     render.main(["--scene", "empty", "--width", "48", "--height", "32", "--samples", "256", "--adaptive", "--target-error", "0.05",
                  "--out", str(out)])
     assert out.exists() and out.stat().st_size > 0
+
+
+# ---------------------------------------------------------------- the density from injected error states
+SHARES = (0.1, 0.25, 1.0)
+
+
+@pytest.fixture(scope="module")
+def pool():
+    return es.pool()
+
+
+@pytest.fixture(scope="module")
+def handles():
+    """one handle per frame for the whole module (the 1920 x 1080 one is made once)"""
+    made = {}
+
+    def get(W, H, K=1, pipelining=None):
+        key = (W, H, K, pipelining)
+        if key not in made:
+            made[key] = _renderer(_cornell(W, H), K, pipelining=pipelining)
+        return made[key]
+    yield get
+    for r in made.values():
+        r.close()
+
+
+def _load(r, acc, mom):
+    r.load_packed_accumulators(acc)
+    r.load_moments(mom)
+
+
+def _device_M(r, FB):
+    """M of the density in force, with the two invariants asserted on the device's own values"""
+    M = ar.from_density(r.sample_density())
+    assert int(M.sum(dtype=np.uint64)) == FB * ar.UNIT and int(M.min()) >= 1
+    return M
+
+
+def _assert_update(r, acc, mom, floor, share, terms=None):
+    FB = acc.shape[1]
+    t = ar.terms(acc, mom, floor) if terms is None else terms
+    m = ar.density_from_terms(t, share)
+    r.update_sample_density(floor, share)
+    M = _device_M(r, FB)
+    want = ar.quantise(m)
+    bad = np.flatnonzero(M != want)
+    assert bad.size == 0, (floor, share, len(bad), bad[:5], M[bad[:5]], want[bad[:5]])
+    return t, m, M
+
+
+@pytest.mark.parametrize("W,H", es.FRAMES)
+def test_density_from_injected_states_equals_the_restatement(W, H, pool, handles):
+    """update_sample_density() on the injected states that have a finite term -- the well-scaled classes; with the subnormal,
+    L = 0 and float32-overflowing ones; with the overflowed moments and n < 2 pixels as well -- for uniform_share 0.1, 0.25, 1 and
+    floor 0, 0.001: M equals quantise(density_from_terms(terms(acc, mom, floor), share)) as integers."""
+    r = handles(W, H)
+    FB = W * H
+    for allowed in (es.BASE, es.NO_FEW, es.ALL):
+        cls, acc, mom = es.state(pool, FB, allowed)
+        _load(r, acc, mom)
+        for floor in (0.0, 0.001):
+            t = ar.terms(acc, mom, floor)
+            if allowed is not es.BASE and FB >= 576:
+                assert np.isinf(t).any() and np.isfinite(t).any()      # terms to be clipped beside finite ones
+            for share in SHARES:
+                _, m, M = _assert_update(r, acc, mom, floor, share, terms=t)
+                if share == 1.0:
+                    assert (M == ar.UNIT).all()
+                elif allowed is es.BASE:
+                    assert M.min() < ar.UNIT < M.max()
+    r.set_sample_density(None)
+
+
+@pytest.mark.parametrize("W,H", es.FRAMES)
+def test_density_clip_flat_and_no_finite_term(W, H, pool, handles):
+    """A pixel whose finite term lies above 16 x the mean is clipped to it; every finite term 0 gives the flat density; no finite
+    term is refused with CL2_E_STATE and leaves the density that was in force."""
+    from clive2_amd.renderer import RendererError
+    r = handles(W, H)
+    FB = W * H
+    cls, acc, mom = es.state(pool, FB, es.BASE)
+    k = int(np.flatnonzero(cls == es.ORDINARY)[len(np.flatnonzero(cls == es.ORDINARY)) // 2])
+    mom = mom.copy()
+    mom[:, k] = pool[2][:, 0] * np.float32(1e6)                          # the pool's first state (n = 2) with a million-fold spread
+    acc = acc.copy()
+    acc[:, k] = pool[1][:, 0]
+    _load(r, acc, mom)
+    t, m, M = _assert_update(r, acc, mom, 0.001, 0.25)
+    mean = er.grid_sum(np.where(np.isfinite(t), t, 0)) / np.isfinite(t).sum()
+    assert np.isfinite(t[k]) and t[k] > ar.KAPPA * mean
+    assert m[k] == np.float32(0.25 + 0.75 * ar.KAPPA) and M[k] == M.max()
+    clipped = M.copy()
+    # every finite term 0: moments all zero (S = 0), uncovered pixels beside them
+    zero = np.zeros_like(mom)
+    _load(r, acc, zero)
+    t, m, M = _assert_update(r, acc, zero, 0.001, 0.25)
+    assert not t.any() and (M == ar.UNIT).all()
+    # no finite term: every pixel covered with n = 1
+    m_fixed = (1.0 + 0.5 * np.cos(np.arange(FB))).astype(np.float32)
+    r.set_sample_density(m_fixed)
+    before = r.sample_density().copy()
+    assert np.array_equal(ar.from_density(before), ar.quantise(m_fixed))
+    fa, fm = es.few_pixel(pool)
+    a1, m1 = np.repeat(fa[:, None], FB, 1), np.repeat(fm[:, None], FB, 1)
+    _load(r, a1, m1)
+    assert np.isinf(ar.terms(a1, m1, 0.001)).all() and ar.density_from_terms(ar.terms(a1, m1, 0.001), 0.25) is None
+    with pytest.raises(RendererError, match=r"\(-3\)"):
+        r.update_sample_density(0.001, 0.25)
+    assert r.sample_density().tobytes() == before.tobytes()
+    # and the clipped state again, after the refusal: the same integers
+    _load(r, acc, mom)
+    r.update_sample_density(0.001, 0.25)
+    assert np.array_equal(_device_M(r, FB), clipped)
+    r.set_sample_density(None)
+
+
+# ---------------------------------------------------------------- mapped passes where C leaves 32 bits
+def _far_density(W, H):
+    """_fixed_density scaled to the frame, plus a block of weight-8 pixels in the last rows: the slots of the last pixels lie far
+    from their own index"""
+    d = _fixed_density(W, H)
+    d[H - H // 8:, W // 4: W // 2] = 8.0
+    return d
+
+
+@pytest.mark.parametrize("W,H", [(320, 240), (1920, 1080)])
+def test_camera_samples_where_the_prefix_sum_passes_32_bits(W, H, handles):
+    """K = 2, pipelined, three passes of a fixed non-uniform density at 76,800 and 2,073,600 pixels (C ends at 5.03e9 and
+    1.36e11): every pixel's camera samples equal the numpy expansion, and acc row 7 is 3 K everywhere."""
+    K = 2
+    FB = W * H
+    r = handles(W, H, K, 2)
+    r.reset_accumulators()
+    r.set_sample_density(_far_density(W, H))
+    M = _device_M(r, FB)
+    assert np.array_equal(M, ar.quantise(_far_density(W, H)))
+    C = ar.prefix(M)
+    assert int(C[-1]) == FB * ar.UNIT > 1 << 32
+    lo, hi = ar.ranges(C, 0)
+    assert np.abs(lo - np.arange(FB)).max() > FB // 64                    # slots far from their pixels
+    r.run_samples(3)                               # the handle's first passes with a density: numbers 0, 1, 2
+    want = ar.camera_samples(C, 0, 3, K)
+    got = r.camera_samples().reshape(-1)
+    bad = np.flatnonzero(got != want.astype(np.float32))
+    assert bad.size == 0, (len(bad), bad[:5], got[bad[:5]], want[bad[:5]])
+    assert (r.packed_accumulators().reshape(8, -1)[7] == 3 * K).all()
+    r.set_sample_density(None)
+    r.reset_accumulators()
+
+
+def test_one_pass_at_320x240_matches_the_float32_restatement():
+    """test_one_pass_matches_the_float32_restatement at 320 x 240, where slot indices pass 65,536 and C passes 2^32: one mapped pass
+    (test variant, debug flag 4) against adaptive_reference.finalize_accumulate, accumulators and moments bit for bit at the
+    pixels restated -- the first and last rows and columns, the border of the weight-8 block (inside and outside), and a seeded
+    draw of 1,500 of the pixels whose slots lie above 65,536; at least 2,000 pixels, at least 500 of them with slots above
+    65,536.  The camera sample counts are compared at every pixel."""
+    W, H = 320, 240
+    FB = W * H
+    r = _renderer(_cornell(W, H), 1, variant="test")
+    r.set_debug_flags(4)
+    r.set_sample_density(_far_density(W, H))
+    M = ar.from_density(r.sample_density())
+    C = ar.prefix(M)
+    r.run_samples(1)
+    agg_rec = r.export_aggregators().view(np.float32).reshape(FB, 32)
+    agg = np.zeros((13, FB), np.float32)
+    agg[:9] = agg_rec[:, :9].T
+    agg[9:12] = agg_rec[:, 12:15].T
+    agg[12] = agg_rec[:, 16]
+    uni = r.export_sample_images()["unidirectional"].reshape(-1, 4).astype(np.float32)
+    lo, hi = ar.ranges(C, ar.offset(0, 0))
+    y, x = np.divmod(np.arange(FB), W)
+    edge = (y == 0) | (y == H - 1) | (x == 0) | (x == W - 1)
+    y0, x0, x1 = H - H // 8, W // 4, W // 2
+    near_block = (y >= y0 - 2) & (x >= x0 - 2) & (x < x1 + 2)
+    deep = (y >= y0 + 1) & (x >= x0 + 1) & (x < x1 - 1)
+    border = near_block & ~deep
+    high = np.flatnonzero((lo >= 65536) & (hi > lo))
+    draw = np.random.RandomState(4).choice(high, 1500, replace=False)
+    pixels = np.unique(np.concatenate([np.flatnonzero(edge | border), draw]))
+    assert len(pixels) >= 2000 and np.isin(pixels, high).sum() >= 500
+    acc = np.zeros((8, FB), np.float32)
+    mom = np.zeros((8, FB), np.float32)
+    n = ar.finalize_accumulate(agg, np.zeros((FB, 4), np.float32), uni, acc, mom, C, ar.inv_density(M), 0, W, H, pixels=pixels)
+    assert np.array_equal(r.camera_samples().reshape(-1), n.astype(np.float32))
+    got, gmom = r.packed_accumulators().reshape(8, -1), r.moments().reshape(8, -1)
+    assert got[:, pixels].tobytes() == acc[:, pixels].tobytes(), pixels[np.argwhere(got[:, pixels] != acc[:, pixels])[:5, 1]]
+    assert gmom[:, pixels].tobytes() == mom[:, pixels].tobytes()
+    assert (got[3, pixels] > 0).sum() > 1000
+    r.close()

@@ -1,10 +1,16 @@
 """Error tracking on the device: the moment sums against their float32 restatement (tests/error_reference.py) on the stage,
 fused and import paths, the derived standard errors and frame metric, that tracking changes nothing else, render_until's
-stopping rule, the validity rules of the moments, and the estimate's calibration on real renders."""
+stopping rule, the validity rules of the moments, and the estimate's calibration on real renders.
+
+The standard errors and the frame metric are also computed from injected states (tests/error_states.py: every branch of
+err_pixel in every wave of some workgroups, frames from less than a wave to the 8 grid-stride trips of 1920 x 1080) and
+compared with the restatement bit for bit -- the frame metric's sum in the device's reduction order (error_reference.grid_sum)
+-- and the device's S is held against the residual sum of squares of the addends that made its moments."""
 import numpy as np
 import pytest
 
 import error_reference as er
+import error_states as es
 from test_gpu_denoise import _cornell, _glass, _open_scene
 
 pytestmark = pytest.mark.gpu
@@ -95,11 +101,11 @@ def test_standard_error_and_frame_metric_match_numpy():
     want = er.standard_error(acc, mom, r.pixel_height, r.pixel_width)
     assert se.shape == (48, 64, 4) and se.dtype == np.float32
     assert np.isfinite(se).all() and (se > 0).any()
-    np.testing.assert_allclose(se, want, rtol=1e-6, atol=0)
+    assert se.view(np.uint32).tobytes() == want.view(np.uint32).tobytes()
     for floor in (0.0, 0.01, 0.05, 0.5):
         e = r.relative_error(floor)
         assert np.isfinite(e)
-        assert e == pytest.approx(er.relative_error(acc, mom, floor), rel=1e-12)
+        assert np.float64(e).tobytes() == np.float64(er.relative_error(acc, mom, floor)).tobytes()
     assert r.standard_error().tobytes() == se.tobytes()
     a, b = np.float64(r.relative_error(0.05)), np.float64(r.relative_error(0.05))
     assert a.tobytes() == b.tobytes()
@@ -209,3 +215,162 @@ def test_estimate_is_calibrated_on_real_renders():
           f"-> {e128 / e32:.3f}")
     assert 0.6 <= med <= 1.6
     assert 0.4 <= e128 / e32 <= 0.6
+
+
+# ---------------------------------------------------------------- injected states
+FLOORS = (0.0, 0.001, 0.05, 0.5)
+
+
+@pytest.fixture(scope="module")
+def pool():
+    return es.pool()
+
+
+@pytest.fixture(scope="module")
+def handles():
+    """one handle per frame for the whole module (the 1920 x 1080 one is made once)"""
+    made = {}
+
+    def get(W, H):
+        if (W, H) not in made:
+            made[W, H] = _renderer(_cornell(W, H), 1)
+        return made[W, H]
+    yield get
+    for r in made.values():
+        r.close()
+
+
+def _load(r, acc, mom):
+    r.load_packed_accumulators(acc)
+    r.load_moments(mom)
+
+
+def _bits64(x):
+    return np.float64(x).tobytes()
+
+
+def _assert_metric(r, acc, mom, floors=FLOORS):
+    """relative_error at every floor equals the grid_sum restatement bit for bit; returns the values"""
+    out = []
+    for floor in floors:
+        got, want = r.relative_error(floor), er.relative_error(acc, mom, floor)
+        assert _bits64(got) == _bits64(want), (floor, got, want)
+        out.append(got)
+    return out
+
+
+@pytest.mark.parametrize("W,H", es.FRAMES)
+def test_injected_states_standard_error_and_metric_bitwise(W, H, pool, handles):
+    """Per frame: (1) every class (error_states.ALL): standard_error() bit for bit, no NaN, the frame metric +inf (covered pixels
+    with n < 2); (2) without the n < 2 and overflowed pixels: +inf at floor 0 from the L + floor = 0 pixels, finite from floor
+    0.001 on, bit for bit; (3) the well-scaled classes: finite and bit for bit at every floor, the same bytes on a second call."""
+    r = handles(W, H)
+    FB = W * H
+    cls, acc, mom = es.state(pool, FB, es.ALL)
+    if FB >= 576:
+        assert set(np.unique(cls)) == set(es.ALL)
+    _load(r, acc, mom)
+    se = r.standard_error()
+    want = er.standard_error(acc, mom, H, W)
+    assert not np.isnan(se).any()
+    bad = np.argwhere(se.view(np.uint32) != want.view(np.uint32))
+    assert bad.size == 0, (len(bad), [(cls[y * W + x], se[y, x, c], want[y, x, c]) for y, x, c in bad[:5]])
+    assert (se.reshape(-1, 4)[cls == es.UNCOVERED] == 0).all() and np.isinf(se.reshape(-1, 4)[cls == es.FEW]).all()
+    if (cls == es.TINY).any():
+        assert (se.reshape(-1, 4)[cls == es.TINY] > 0).any()          # subnormal sums read as their values, not flushed
+    assert r.standard_error().tobytes() == se.tobytes()
+    if (cls == es.FEW).any():
+        assert _assert_metric(r, acc, mom) == [np.inf] * 4
+
+    cls, acc, mom = es.state(pool, FB, es.NO_FEW)
+    _load(r, acc, mom)
+    e = _assert_metric(r, acc, mom)
+    if (cls == es.SIGNED).any():
+        assert e[0] == np.inf and np.isfinite(e[1:]).all(), e
+
+    cls, acc, mom = es.state(pool, FB, es.BASE)
+    _load(r, acc, mom)
+    e = _assert_metric(r, acc, mom)
+    assert np.isfinite(e).all() and all(x > 0 for x in e), e
+    assert _bits64(r.relative_error(0.05)) == _bits64(e[2])
+    se = r.standard_error()
+    assert se.view(np.uint32).tobytes() == er.standard_error(acc, mom, H, W).view(np.uint32).tobytes()
+
+
+@pytest.mark.parametrize("W,H", es.FRAMES)
+def test_injected_states_frame_outcomes(W, H, pool, handles):
+    """The frame-level branches on the well-scaled state: one covered pixel with n < 2 (n = 1, exactly noiseless: S * scale would be
+    0 * inf) in the frame's last wave, in the last wave of the grid's last workgroup and, from 262,145 pixels on, in a second-trip
+    position makes the metric
+    +inf; nothing covered: +inf; covered pixels in one workgroup only, and only pixel FB - 1 covered: finite, bit for bit."""
+    r = handles(W, H)
+    FB = W * H
+    cls, acc, mom = es.state(pool, FB, es.BASE)
+    fa, fm = es.few_pixel(pool)
+    spots = [FB - 1 - (FB - 1) % 64 + min(3, (FB - 1) % 64)]            # in the frame's last wave
+    if FB >= 1024 * 256:
+        spots.append(1023 * 256 + 192 + 3)                               # workgroup 1,023 of 1,024, its last wave
+    if FB > 1024 * 256:
+        spots.append(1024 * 256 + 256 + 70)                              # workgroup 1's second trip, its second wave
+    for p in spots:
+        a, m = acc.copy(), mom.copy()
+        a[:, p], m[:, p] = fa, fm
+        _load(r, a, m)
+        assert _assert_metric(r, a, m, (0.0, 0.05)) == [np.inf, np.inf]
+        se = r.standard_error().reshape(-1, 4)
+        assert np.isinf(se[p]).all() and se.view(np.uint32).tobytes() == er.standard_error(a, m).view(np.uint32).tobytes()
+    # nothing covered
+    a = acc.copy()
+    a[3] = np.where(np.arange(FB) % 2 == 0, np.float32(0.0), np.float32(np.nan))
+    _load(r, a, mom)
+    assert _assert_metric(r, a, mom, (0.0, 0.05)) == [np.inf, np.inf]
+    assert not r.standard_error().any()
+    # covered pixels in one workgroup only (its first-trip pixels); every other partial is (0, 0, 0)
+    b = min(3, (FB - 1) // 256)
+    inside = (np.arange(FB) >= 256 * b) & (np.arange(FB) < 256 * b + 256)
+    a = acc.copy()
+    a[3] = np.where(inside, acc[3], np.float32(0.0))
+    _load(r, a, mom)
+    e = _assert_metric(r, a, mom)
+    assert np.isfinite(e).all() and e[1] > 0
+    # only the last pixel covered
+    a, m = acc.copy(), mom.copy()
+    a[3] = 0.0
+    a[:, FB - 1], m[:, FB - 1] = pool[1][:, 0], pool[2][:, 0]            # the pool's first state: ordinary, n = 2
+    _load(r, a, m)
+    e = _assert_metric(r, a, m)
+    assert np.isfinite(e).all() and e[1] > 0
+    _, var, L = er.variances(a[:, FB - 1:], m[:, FB - 1:])
+    assert e[2] == np.sqrt(var[0, 3] / ((L[0] + 0.05) * (L[0] + 0.05)))
+
+
+@pytest.mark.parametrize("W,H", [(41, 25), (512, 513)])
+@pytest.mark.parametrize("n", [2, 8, 64])
+def test_device_estimate_against_the_residual_sum_of_squares(W, H, n, handles):
+    """The addends of every regime of test_error_estimate_cpu.test_float32_restatement_is_inside_the_derived_bound through
+    import_sample_images + process_images, so that the moments are k_accumulate<true>'s own: they equal add_moments' bit for
+    bit, and standard_error() stays inside |S - S*| <= 8 n u T against the float64 residual sums of the same addends (the bound
+    and its two consequences: see that test's docstring).  The regimes share the frame: pixel p is of regime p mod 5."""
+    r = handles(W, H)
+    FB = W * H
+    seqs = [es.addend_sequence(regime, FB, n, seed=2000 + n) for regime in es.REGIMES]
+    which = np.arange(FB) % len(es.REGIMES)
+    xs = [np.choose(which[:, None], [s[0][i] for s in seqs]).astype(np.float32) for i in range(n)]
+    ws = [np.choose(which, [s[1][i] for s in seqs]).astype(np.float32) for i in range(n)]
+    r.reset_accumulators()
+    zero4 = np.zeros((FB, 4), np.float32)
+    for x, w in zip(xs, ws):
+        fin = np.concatenate([x, np.ones((FB, 1), np.float32)], axis=1)
+        r.import_sample_images(finalized=fin, light=zero4, sample_weights=w, unidirectional=zero4)
+        r.process_images()
+    acc_ref, mom_ref = es.accumulate(xs, ws)
+    acc = r.packed_accumulators().reshape(8, -1)
+    assert r.moments().reshape(8, -1).tobytes() == mom_ref.tobytes()
+    assert acc[:4].tobytes() == acc_ref[:4].tobytes() and (acc[7] == n).all()
+    se = r.standard_error()
+    assert se.view(np.uint32).tobytes() == er.standard_error(acc, mom_ref, H, W).view(np.uint32).tobytes()
+    Sstar, T = er.residual_sums(xs, ws)
+    for k, regime in enumerate(es.REGIMES):
+        at = which == k
+        er.check_against_residual_sums(se.reshape(-1, 4)[at], acc[:, at], Sstar[at], T[at], n, f"device {W}x{H} {regime} n={n}")
+    r.reset_accumulators()
