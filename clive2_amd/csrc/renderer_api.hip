@@ -20,6 +20,7 @@
 #include "../../include/clive2_amd.h"
 #include "kernels.hpp"
 #include "denoise.hpp"
+#include "denoise_guided.hpp"
 #include "error_estimate.hpp"
 #include "adaptive.hpp"
 #include "tonemap.hpp"
@@ -146,6 +147,7 @@ struct cl2_renderer {
     bool features_valid = false;         // cleared by cl2_upload_scene
     float4* d_dn[2] = {nullptr, nullptr};   // ping-pong colour of the filter passes
     float* d_dn_out = nullptr;           // (H, W, 3) result of the last pass
+    float* d_dn_var = nullptr;           // (H, W) guide variance after the last pass of cl2_denoise_guided (denoise_guided.hpp)
 
     // error tracking (cl2_set_error_tracking, error_estimate.hpp): second moments of the addends, [8][W*H], while tracking is on
     float* d_mom = nullptr;
@@ -1997,6 +1999,18 @@ int cl2_read_features(cl2_renderer* r, float* g0, float* g1, size_t n_pixels) {
     return CL2_OK;
 }
 
+namespace {
+// working buffers of both filters (cl2_denoise, cl2_denoise_guided), allocated by the first call of either
+int need_filter_buffers(cl2_renderer* r) {
+    if (r->d_dn_out) return CL2_OK;
+    const size_t FB = (size_t)r->FB;
+    int rc = dev_alloc(r, &r->d_dn[0], FB);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_dn[1], FB);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_dn_out, 3 * FB);     // last: its presence says the set is complete
+    return rc;
+}
+}  // namespace
+
 int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* out_bgr,
                 size_t n_floats) {
     STAGE_PROLOGUE(r);
@@ -2007,12 +2021,7 @@ int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
     if (bad(sigma_color) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
     if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
     const size_t FB = (size_t)r->FB;
-    if (!r->d_dn_out) {
-        int rc = dev_alloc(r, &r->d_dn[0], FB);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_dn[1], FB);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_dn_out, 3 * FB);
-        if (rc != CL2_OK) return rc;
-    }
+    TRY(need_filter_buffers(r));
     hipStream_t st = r->stream;
     hipLaunchKernelGGL(k_denoise_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc, r->d_dn[0],
                        iterations == 0 ? r->d_dn_out : (float*)nullptr);
@@ -2205,6 +2214,48 @@ int cl2_read_standard_error(cl2_renderer* r, float* out, size_t n_floats) {
         rc = fail(r, CL2_E_HIP, "standard error download failed");
     (void)hipFree(d);
     return rc;
+}
+
+// The variance-guided filter (denoise_guided.hpp): cl2_denoise's passes with the luma edge-stop driven by the moments.
+int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
+                       size_t n_floats, float* out_var, size_t n_var) {
+    STAGE_PROLOGUE(r);
+    if (!out_bgr) return fail(r, CL2_E_INVALID, "NULL output");
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "denoised picture must hold 3*W*H floats");
+    if (out_var ? n_var != (size_t)r->FB : n_var != 0)
+        return fail(r, CL2_E_INVALID, "guide variance must hold W*H floats (or be NULL with n_var 0)");
+    if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
+    auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
+    if (bad(sigma_luma) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
+    if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
+    TRY(need_moments(r));
+    const size_t FB = (size_t)r->FB;
+    TRY(need_filter_buffers(r));
+    if (!r->d_dn_var) TRY(dev_alloc(r, &r->d_dn_var, FB));
+    hipStream_t st = r->stream;
+    float* const dvar = out_var ? r->d_dn_var : nullptr;
+    hipLaunchKernelGGL(k_denoise_guided_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc,
+                       (const float*)r->d_mom, r->d_dn[0], iterations == 0 ? r->d_dn_out : (float*)nullptr, dvar);
+    HIP_TRY(r, hipGetLastError());
+    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
+    const float den_a = sigma_albedo * sigma_albedo;
+    for (int i = 0; i < iterations; i++) {
+        const int step = 1 << i;
+        const float4* cin = r->d_dn[i & 1];
+        float4* cout = r->d_dn[(i + 1) & 1];
+        float* out3 = i == iterations - 1 ? r->d_dn_out : nullptr;
+        if (step == 1)
+            hipLaunchKernelGGL(k_denoise_guided_pass<1>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        else if (step == 2)
+            hipLaunchKernelGGL(k_denoise_guided_pass<2>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        else
+            hipLaunchKernelGGL(k_denoise_guided_pass<0>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        HIP_TRY(r, hipGetLastError());
+    }
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(out_bgr, r->d_dn_out, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_var) HIP_TRY(r, hipMemcpy(out_var, r->d_dn_var, n_var * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 int cl2_relative_error(cl2_renderer* r, double floor, double* out) {

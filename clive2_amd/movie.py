@@ -47,6 +47,9 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true",
                     help="after each frame's samples, render its first-hit features and save the denoised picture (Renderer.denoised_image)")
     ap.add_argument("--feature-samples", type=int, default=4, help="camera rays per pixel of the feature pass of --denoise")
+    ap.add_argument("--variance-guided", action="store_true",
+                    help="with --denoise: the filter whose edge-stop follows the per-pixel error estimate (Renderer.guided_image, "
+                         "DESIGN.md 6.6).  Turns error tracking on before each frame's first sample")
     ap.add_argument("--target-error", type=float, default=None,
                     help="render each frame until its relative error (Renderer.relative_error) is at most this, --samples as the cap")
     ap.add_argument("--error-floor", type=float, default=None,
@@ -66,6 +69,8 @@ def main(argv=None):
         ap.error("--check-every must be >= 1")
     if args.adaptive and args.target_error is None:
         ap.error("--adaptive needs --target-error")
+    if args.variance_guided and not args.denoise:
+        ap.error("--variance-guided needs --denoise")
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
 
@@ -87,6 +92,8 @@ def main(argv=None):
                 raise
             renderer = Renderer(scene, device=0)     # the launcher exposes one GPU per rank: it is device 0
         note = ""
+        if args.variance_guided:
+            renderer.set_error_tracking(True)
         if args.target_error is not None:
             _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every,
                                                adaptive=args.adaptive, uniform_share=args.uniform_share)
@@ -96,7 +103,7 @@ def main(argv=None):
         # a frame leaves the device tone-mapped (6 MB at 1080p; Renderer.image reads 66 MB of accumulators and maps them with numpy)
         if args.denoise:
             renderer.render_features(args.feature_samples)
-            image = renderer.denoised_image
+            image = renderer.guided_image if args.variance_guided else renderer.denoised_image
         else:
             image = renderer.image if args.host_tonemap else renderer.tone_mapped("image")
         save_frame(os.path.join(out_dir, f"frame_{f:04d}.png"), image)

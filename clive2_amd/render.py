@@ -4,6 +4,7 @@ instead of opening a cv2 window (display code is out of scope).
     python -m clive2_amd.render --scene empty --width 1280 --height 720 --samples 64 --out cornell.png
     python -m clive2_amd.render --scene empty --samples 4 --denoise --out cornell_denoised.png
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --error-out err.npy
+    python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --denoise --variance-guided --out cornell_guided.png
 
 Several GPUs: start one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE in the environment (e.g.
 `python -m torch.distributed.run --nproc-per-node N -m clive2_amd.render ...`; any spawner will do, torch
@@ -42,6 +43,9 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true",
                     help="after the samples, render the first-hit features and write the denoised picture (Renderer.denoised_image)")
     ap.add_argument("--feature-samples", type=int, default=4, help="camera rays per pixel of the feature pass of --denoise")
+    ap.add_argument("--variance-guided", action="store_true",
+                    help="with --denoise: the filter whose edge-stop follows the per-pixel error estimate (Renderer.guided_image, "
+                         "DESIGN.md 6.6): it closes where the picture has converged.  Turns error tracking on before the first sample")
     ap.add_argument("--target-error", type=float, default=None,
                     help="render until the relative error e (Renderer.relative_error) is at most this, with --samples as the cap "
                          "(one rank only)")
@@ -65,6 +69,8 @@ def main(argv=None):
         ap.error("--check-every must be >= 1")
     if args.adaptive and args.target_error is None:
         ap.error("--adaptive needs --target-error")
+    if args.variance_guided and not args.denoise:
+        ap.error("--variance-guided needs --denoise")
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
 
@@ -81,7 +87,7 @@ def main(argv=None):
     K = renderer.streams
     if args.reproducible:
         renderer.set_reproducible(True)
-    if args.target_error is not None or args.error_out:
+    if args.target_error is not None or args.error_out or args.variance_guided:
         renderer.set_error_tracking(True)
     # seed buffers of the job: stream k of rank r is buffer r * K + k
     renderer.set_seeds(stream_seeds(args.width * args.height, K, first_rank=rank * K))
@@ -133,7 +139,7 @@ def main(argv=None):
     if args.denoise:
         t1 = time.time()
         renderer.render_features(args.feature_samples)
-        image = renderer.denoised_image
+        image = renderer.guided_image if args.variance_guided else renderer.denoised_image
         print(f"[rank {rank}] features ({args.feature_samples} rays per pixel) and denoising took {time.time() - t1:.2f} seconds")
     else:
         image = renderer.tone_mapped("image") if args.device_tonemap else renderer.image
