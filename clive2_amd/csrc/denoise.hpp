@@ -15,8 +15,8 @@
 //
 // Filter (cl2_denoise): c = scrub(acc_image / acc_weight) as Renderer.radiance computes it; `iterations` passes of the
 // 5 x 5 B3-spline a-trous kernel at steps 1, 2, 4, ..., each tap weighted by the normals, depths and albedos of the two
-// pixels and by the distance of their colours after x = c / (1 + luma(c)).  Pixels without coverage pass through, taps
-// on them or outside the frame are skipped.  tests/denoise_reference.py restates every operation below in numpy, in
+// pixels and by the distance of their colours after x = c / (1 + luma(c)).  Pixels without coverage pass through, and so do
+// pixels whose weight sum is not greater than 0 (NaN included); taps without coverage or outside the frame are skipped.  tests/denoise_reference.py restates every operation below in numpy, in
 // the same order.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -172,7 +172,9 @@ __global__ __launch_bounds__(DN_TILE * DN_TILE) void k_denoise_pass(int W, int H
                 s0 += w * cq.x; s1 += w * cq.y; s2 += w * cq.z;
             }
         }
-        if (sw > 0.0f) { o0 = s0 / sw; o1 = s1 / sw; o2 = s2 / sw; }   // sw is 0 only for a pixel whose normals cancelled
+        // A weight sum that is not greater than 0 keeps the colour: 0 for a pixel whose normal is 0, NaN when a denominator is 0
+        // (depth 0, or sigma_depth * z_p underflowing: the centre tap's 0 / 0); cl2_denoise refuses den_c and den_a below FLT_MIN.
+        if (sw > 0.0f) { o0 = s0 / sw; o1 = s1 / sw; o2 = s2 / sw; }
     }
     if (out3) { out3[3 * (size_t)p] = o0; out3[3 * (size_t)p + 1] = o1; out3[3 * (size_t)p + 2] = o2; }
     else cout[p] = make_float4(o0, o1, o2, 0.0f);

@@ -7,6 +7,7 @@
 // the host between samples.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -847,7 +848,7 @@ int alloc_pixel_state(cl2_renderer* r) {
 
 extern "C" {
 
-int cl2_abi_version(void) { return 5; }
+int cl2_abi_version(void) { return 6; }
 
 int cl2_build_bvh(const double* tri_min, const double* tri_max, int64_t n_triangles, int max_members, int max_depth,
                   void* out_boxes, int64_t box_capacity, int64_t* n_boxes_out, int64_t* out_perm) {
@@ -1938,26 +1939,33 @@ int cl2_probe_traverse(cl2_renderer* r, const void* rays_v, size_t n_rays, int32
 }
 
 // ---- first-hit features and the denoiser (denoise.hpp) ----
+namespace {
+// the feature set (cl2_render_features, cl2_write_features), allocated by the first call of either
+int need_feature_buffers(cl2_renderer* r) {
+    if (r->d_g0) return CL2_OK;
+    const size_t FB = (size_t)r->FB;
+    int rc = dev_alloc(r, &r->d_feat_seeds, FB);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_o, FB);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_d, FB);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_hit, FB);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_count, (size_t)1);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_work, (size_t)WORK_STRIDE);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_stats, (size_t)1);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_g1, FB);
+    if (rc != CL2_OK) return rc;
+    const unsigned n = (unsigned)FB;
+    HIP_TRY(r, hipMemcpy(r->d_feat_count, &n, sizeof n, hipMemcpyHostToDevice));
+    return dev_alloc(r, &r->d_g0, FB);                              // last: its presence says the set is complete
+}
+}  // namespace
+
 int cl2_render_features(cl2_renderer* r, const uint32_t* seeds, size_t n_words, int samples) {
     STAGE_PROLOGUE(r);
     if (!seeds) return fail(r, CL2_E_INVALID, "NULL seed buffer");
     if (n_words != 2 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "feature seeds: 2 words per pixel of the frame ((W*H, 2) uint32)");
     if (samples < 1 || samples > 65536) return fail(r, CL2_E_INVALID, "feature samples must be in 1..65536");
     const size_t FB = (size_t)r->FB;
-    if (!r->d_g0) {
-        int rc = dev_alloc(r, &r->d_feat_seeds, FB);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_o, FB);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_d, FB);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_hit, FB);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_count, (size_t)1);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_work, (size_t)WORK_STRIDE);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_feat_stats, (size_t)1);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_g1, FB);
-        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_g0, FB);     // last: its presence says the set is complete
-        if (rc != CL2_OK) return rc;
-        const unsigned n = (unsigned)FB;
-        HIP_TRY(r, hipMemcpy(r->d_feat_count, &n, sizeof n, hipMemcpyHostToDevice));
-    }
+    TRY(need_feature_buffers(r));
     r->features_valid = false;
     hipStream_t st = r->stream;
     HIP_TRY(r, hipMemcpyAsync(r->d_feat_seeds, seeds, FB * sizeof(uint2), hipMemcpyHostToDevice, st));
@@ -1999,6 +2007,20 @@ int cl2_read_features(cl2_renderer* r, float* g0, float* g1, size_t n_pixels) {
     return CL2_OK;
 }
 
+// The counterpart of cl2_read_features: the filters then read these buffers as if cl2_render_features had made them.
+int cl2_write_features(cl2_renderer* r, const float* g0, const float* g1, size_t n_pixels) {
+    STAGE_PROLOGUE(r);
+    if (!g0 || !g1) return fail(r, CL2_E_INVALID, "NULL feature array");
+    if (n_pixels != (size_t)r->FB) return fail(r, CL2_E_INVALID, "feature arrays must hold W*H float4 entries");
+    TRY(need_feature_buffers(r));
+    r->features_valid = false;
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(r->d_g0, g0, n_pixels * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(r, hipMemcpy(r->d_g1, g1, n_pixels * sizeof(float4), hipMemcpyHostToDevice));
+    r->features_valid = true;
+    return CL2_OK;
+}
+
 namespace {
 // working buffers of both filters (cl2_denoise, cl2_denoise_guided), allocated by the first call of either
 int need_filter_buffers(cl2_renderer* r) {
@@ -2019,6 +2041,10 @@ int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
     if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
     auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
     if (bad(sigma_color) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
+    // a denominator below the smallest normal float32 (0 or subnormal) would turn every weight into 0/0 or an untested division
+    if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
+    if (iterations >= 1 && std::ldexp(sigma_color * sigma_color, -2 * (iterations - 1)) < FLT_MIN)
+        return fail(r, CL2_E_INVALID, "sigma_color^2 * 4^-(iterations-1) underflows float32");
     if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
     const size_t FB = (size_t)r->FB;
     TRY(need_filter_buffers(r));
@@ -2227,6 +2253,7 @@ int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float 
     if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
     auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
     if (bad(sigma_luma) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
+    if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
     if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
     TRY(need_moments(r));
     const size_t FB = (size_t)r->FB;

@@ -477,6 +477,15 @@ class Renderer:
         self._check(self._L.cl2_read_features(self._h, ptr(g0), ptr(g1), C.c_size_t(H * W)), "cl2_read_features")
         return dict(normal=g0[..., :3], depth=g0[..., 3], albedo=g1[..., :3], coverage=g1[..., 3])
 
+    def load_features(self, normal, depth, albedo, coverage):
+        """Write the guide buffers (the counterpart of features(), same shapes): they become the current features of the
+        uploaded scene, as if render_features() had made them.  The render state is not touched."""
+        H, W = self.pixel_height, self.pixel_width
+        g0, g1 = np.empty((H, W, 4), np.float32), np.empty((H, W, 4), np.float32)
+        g0[..., :3], g0[..., 3] = np.reshape(normal, (H, W, 3)), np.reshape(depth, (H, W))
+        g1[..., :3], g1[..., 3] = np.reshape(albedo, (H, W, 3)), np.reshape(coverage, (H, W))
+        self._check(self._L.cl2_write_features(self._h, ptr(g0), ptr(g1), C.c_size_t(H * W)), "cl2_write_features")
+
     def denoised_radiance(self, iterations=None, sigma_color=None, sigma_depth=None, sigma_albedo=None):
         """`radiance` after the edge-avoiding a-trous filter guided by the features (render_features() first; a new scene
         needs new features): float32 (H,W,3), BGR.  Unset arguments take DENOISE_DEFAULTS."""

@@ -382,17 +382,26 @@ int cl2_probe_traverse(cl2_renderer* r, const void* rays, size_t n_rays, int32_t
 int cl2_render_features(cl2_renderer* r, const uint32_t* seeds, size_t n_words, int samples);
 /* Both feature buffers as W*H float4 each (n_pixels = W*H).  CL2_E_STATE without current features. */
 int cl2_read_features(cl2_renderer* r, float* g0, float* g1, size_t n_pixels);
+/* The counterpart of cl2_read_features (ABI 6), for features made elsewhere, checkpoints and tests: allocates the feature set if
+ * there is none, copies both W*H float4 arrays as they are and makes them the current features of the uploaded scene (they hold
+ * until the next cl2_upload_scene, like rendered ones).  Touches nothing of the sample pipeline.  The filters expect what
+ * cl2_render_features makes: finite values, coverage 0 where nothing was hit.  CL2_E_INVALID for a NULL array or n_pixels
+ * other than W*H. */
+int cl2_write_features(cl2_renderer* r, const float* g0, const float* g1, size_t n_pixels);
 /* The filtered radiance, (H, W, 3) float32 b, g, r (n_floats = 3*W*H), from the accumulators in place (read, not changed).
  * Input c = scrub(summed_image / summed_sample_weights) (Renderer.radiance); `iterations` passes i = 0, 1, ... with step
- * s = 2^i: a pixel with coverage 0 passes through, every other one becomes sum(w c_q) / sum(w) over the taps
- * q = p + s (dx, dy), dx, dy in -2..2 (dy outer), that lie in the frame and have coverage, with
+ * s = 2^i: a pixel with coverage 0 passes through, every other one becomes sum(w c_q) / sum(w), or keeps its colour when
+ * sum(w) is not greater than 0 (0 for a zero normal; NaN when sigma_depth z_p s is 0, that is depth 0 or an underflow),
+ * over the taps q = p + s (dx, dy), dx, dy in -2..2 (dy outer), that lie in the frame and have coverage, with
  *     w = h(dx) h(dy) max(0, n_p.n_q)^32 exp(-|z_p - z_q| / (sigma_depth z_p s)) exp(-|a_p - a_q|^2 / sigma_albedo^2)
  *         exp(-|x_p - x_q|^2 / (sigma_color^2 4^-i)),   h = (1, 4, 6, 4, 1) / 16,   x = c / (1 + luma(c)).
  * Defaults of the Python binding: iterations 3, sigma_color 2.0, sigma_depth 0.1, sigma_albedo 0.1, settled on the Cornell
  * box and the glass scene at 256 x 192 and 4 samples against 1024-sample pictures: relative MSE 0.29 and 0.26 of the raw
  * picture's (5 passes over-blur the Cornell box's lighting, 0.72; sigma_color 0.6 leaves the glass noisy, 0.49).
  * iterations in 0..12 (0 = the input);
- * sigmas positive and finite.  CL2_E_STATE without current features (none rendered, or a scene uploaded since). */
+ * sigmas positive and finite, and neither sigma_albedo^2 nor, with iterations >= 1, sigma_color^2 4^-(iterations-1) (the float32
+ * values the passes divide by) below FLT_MIN: a denominator that underflowed to 0 or to a subnormal is refused, not
+ * trusted; else CL2_E_INVALID.  CL2_E_STATE without current features (none rendered, or a scene uploaded since). */
 int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* out_bgr,
                 size_t n_floats);
 
@@ -444,8 +453,9 @@ int cl2_read_standard_error(cl2_renderer* r, float* out, size_t n_floats);
  * GUIDE, NOT an error estimate of the filtered picture -- it underestimates that picture's squared error by a factor of 10 to 100.
  * Defaults of the Python binding (Renderer.GUIDED_DEFAULTS): iterations 4, sigma_luma 4.0, sigma_depth 0.1, sigma_albedo 0.1, settled on
  * the Cornell box and the glass scene at 256 x 192 against 1024-sample pictures: relative MSE 0.09 and 0.21 of the raw picture's at 4
- * passes, 0.38 and 0.13 at 256 (the fixed filter: 0.29 and 0.26 at 4 passes, 14 and 0.30 at 256).  iterations in 0..12 (0 = the input); sigmas positive
- * and finite; else CL2_E_INVALID.  CL2_E_STATE without current features, with error tracking off, or with invalid moments.
+ * passes, 0.38 and 0.13 at 256 (the fixed filter: 0.29 and 0.26 at 4 passes, 14 and 0.30 at 256).  iterations in 0..12 (0 = the
+ * input); sigmas positive and finite, sigma_albedo^2 (float32) not below FLT_MIN as for cl2_denoise; else CL2_E_INVALID.
+ * CL2_E_STATE without current features, with error tracking off, or with invalid moments.
  * Touches neither seeds, accumulators, moments, counters nor walk tallies; works with sample streams, with a sample density
  * and after cl2_reduce_accumulators (the moments are valid in all three). */
 int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,

@@ -160,6 +160,9 @@ def test_state_errors():
                  (1, 4.0, 0.0, 0.1, ptr(out), out.size, None, 0),
                  (1, 4.0, 0.1, float("nan"), ptr(out), out.size, None, 0),
                  (1, float("inf"), 0.1, 0.1, ptr(out), out.size, None, 0),
+                 (1, 4.0, 0.1, 1e-23, ptr(out), out.size, None, 0),                 # sigma_albedo^2 underflows to 0
+                 (0, 4.0, 0.1, 1e-23, ptr(out), out.size, None, 0),
+                 (1, 4.0, 0.1, 1e-19, ptr(out), out.size, None, 0),                 # ... to a subnormal (FLT_MIN = 1.1755e-38)
                  (1, 4.0, 0.1, 0.1, ptr(out), out.size, ptr(var), var.size - 1),    # a wrong n_var
                  (1, 4.0, 0.1, 0.1, ptr(out), out.size, None, var.size),
                  (1, 4.0, 0.1, 0.1, ptr(out), out.size - 1, None, 0),
@@ -169,6 +172,7 @@ def test_state_errors():
         with pytest.raises(RendererError, match=r"\(-1\)"):
             r._check(L.cl2_denoise_guided(h, *args[:5], C.c_size_t(args[5]), args[6], C.c_size_t(args[7])), "cl2_denoise_guided")
     assert L.cl2_denoise_guided(h, 12, 4.0, 0.1, 0.1, ptr(out), C.c_size_t(out.size), ptr(var), C.c_size_t(var.size)) == 0
+    assert L.cl2_denoise_guided(h, 12, 1e-23, 0.1, 1.1e-19, ptr(out), C.c_size_t(out.size), None, C.c_size_t(0)) == 0   # 1.21e-38
     r.close()
 
 

@@ -226,7 +226,7 @@ def native_lib():
 def test_library_exports_the_guided_filter(native_lib):
     from clive2_amd import _native
     assert hasattr(native_lib, "cl2_denoise_guided") and "cl2_denoise_guided" in _native.EXPORTS
-    assert native_lib.cl2_abi_version() == 5
+    assert native_lib.cl2_abi_version() == 6
 
 
 def test_guided_filter_refuses_a_null_handle(native_lib):
