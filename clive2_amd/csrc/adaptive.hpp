@@ -146,14 +146,15 @@ __global__ __launch_bounds__(BLOCK) void k_dens_expand(int B, int FB, const uint
 // ---- K6 + process_images of a mapped pass (the counterpart of k_finalize_accumulate<MOMENTS>) ----
 // Per pixel p and plane s: the 3x3 neighbours q in k_finalize_accumulate's (i, j) order; within a neighbour its slots in
 // ascending order, each as (weight invm_q) agg; the unidirectional rows add invm_p scrub(uni) over p's own slots; row 7 += 1 per
-// plane; moments as k_finalize_accumulate.  cam_count[p] += the camera samples p received (n_p summed over the planes).
+// plane; moments and buckets as k_finalize_accumulate.  cam_count[p] += the camera samples p received (n_p summed over the planes).
 // A flat density (invm = 1.0f, one slot per pixel: slot q) performs exactly the float operations of k_finalize_accumulate.
-template <bool MOMENTS>
+template <bool MOMENTS, bool BUCKETS = false>
 __global__ __launch_bounds__(BLOCK) void k_finalize_accumulate_mapped(int B, int W, int H, const float* __restrict__ agg,
                                                                       float4* __restrict__ light_image, const float4* __restrict__ uni,
                                                                       float* __restrict__ acc, float* __restrict__ mom,
                                                                       const uint64_t* __restrict__ C, const float* __restrict__ invm,
-                                                                      uint32_t pass, unsigned* __restrict__ cam_count) {
+                                                                      uint32_t pass, unsigned* __restrict__ cam_count,
+                                                                      float* __restrict__ bkt, int M) {
     const int id = blockIdx.x * BLOCK + threadIdx.x;
     const int FB = W * H;
     if (id >= FB) return;
@@ -198,6 +199,7 @@ __global__ __launch_bounds__(BLOCK) void k_finalize_accumulate_mapped(int B, int
         a[1] += x1;
         a[2] += x2;
         a[3] += w;
+        add_bucket<BUCKETS>(bkt, M, (size_t)FB, (size_t)id, a[7], x0, x1, x2, w);
         int lo, hi;
         dens_range(C, id, u, lo, hi);
         for (int slot = lo; slot < hi; slot++) {

@@ -45,6 +45,7 @@
 #include "bvh_traverse.hpp"
 #include "bvh_wide.hpp"
 #include "scene_layout.hpp"
+#include "robust.hpp"
 
 namespace cl2 {
 
@@ -1259,6 +1260,10 @@ __device__ __forceinline__ float scrub(float x) {   // np.nan_to_num(x, posinf=0
 // (float32, the luma of dn_compress), rows 0..2 += x_c x_c, 3 += w w, 4..6 += x_c w, 7 += y y -- one float32 add per row and
 // addend, in stream order.  MOMENTS = false is the default path and compiles to the same instructions as before the
 // template existed (`mom` is not read).
+//
+// BUCKETS = true (cl2_set_robust_buckets, robust.hpp): every addend also goes into bucket (int)a7 % M of bkt [M][4][FB], a7 = the
+// pixel's row 7 before the addend (add_bucket).  acc and mom get the bytes they get without it; BUCKETS = false compiles to the
+// instructions of the kernels before the parameter existed (`bkt` and `M` are not read).
 template <bool MOMENTS>
 __device__ __forceinline__ void add_moments(float (&m)[8], float x0, float x1, float x2, float w) {
     if constexpr (MOMENTS) {
@@ -1274,11 +1279,11 @@ __device__ __forceinline__ void add_moments(float (&m)[8], float x0, float x1, f
     }
 }
 
-template <bool MOMENTS>
+template <bool MOMENTS, bool BUCKETS = false>
 __global__ __launch_bounds__(BLOCK) void k_accumulate(int FB, int streams, const float4* __restrict__ finalized,
                                                       const float* __restrict__ sample_w, float4* __restrict__ light_image,
                                                       const float4* __restrict__ uni, float* __restrict__ acc,
-                                                      float* __restrict__ mom) {
+                                                      float* __restrict__ mom, float* __restrict__ bkt, int M) {
     const int id = blockIdx.x * BLOCK + threadIdx.x;
     if (id >= FB) return;
     float a[8], m[8];
@@ -1298,6 +1303,7 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate(int FB, int streams, const
         a[1] += x1;
         a[2] += x2;
         a[3] += w;
+        add_bucket<BUCKETS>(bkt, M, (size_t)FB, (size_t)id, a[7], x0, x1, x2, w);
         a[4] += scrub(u.x);
         a[5] += scrub(u.y);
         a[6] += scrub(u.z);
@@ -1318,10 +1324,11 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate(int FB, int streams, const
 // cl2_finalize_samples / cl2_process_images exchange, 36 B per pixel and a launch boundary per sample).
 // Same statements in the same order as k_finalize followed by k_accumulate (moments included).
 // `B` = entries (streams x W x H, the stride of the aggregator rows); one thread per PIXEL adds its streams in order.
-template <bool MOMENTS>
+template <bool MOMENTS, bool BUCKETS = false>
 __global__ __launch_bounds__(BLOCK) void k_finalize_accumulate(int B, int W, int H, const float* __restrict__ agg,
                                                                float4* __restrict__ light_image, const float4* __restrict__ uni,
-                                                               float* __restrict__ acc, float* __restrict__ mom) {
+                                                               float* __restrict__ acc, float* __restrict__ mom,
+                                                               float* __restrict__ bkt, int M) {
     const int id = blockIdx.x * BLOCK + threadIdx.x;
     const int FB = W * H;
     if (id >= FB) return;
@@ -1356,6 +1363,7 @@ __global__ __launch_bounds__(BLOCK) void k_finalize_accumulate(int B, int W, int
         a[1] += x1;
         a[2] += x2;
         a[3] += w;
+        add_bucket<BUCKETS>(bkt, M, (size_t)FB, (size_t)id, a[7], x0, x1, x2, w);
         a[4] += scrub(u.x);
         a[5] += scrub(u.y);
         a[6] += scrub(u.z);

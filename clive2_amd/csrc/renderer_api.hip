@@ -156,6 +156,11 @@ struct cl2_renderer {
     bool acc_clean = true;               // the accumulators hold nothing (cl2_create, cl2_reset_accumulators)
     double* d_err_partial = nullptr;     // frame metric: [3][ERR_BLOCKS] per-workgroup partials + [4] result (first call)
 
+    // robust picture (cl2_set_robust_buckets, robust.hpp): M partial sums per pixel, [M][4][W*H], while the buckets are on
+    float* d_bkt = nullptr;
+    int bkt_M = 0;
+    bool bkt_valid = false;              // every addend in the accumulators also went into the buckets (the rules of mom_valid)
+
     // adaptive sampling (cl2_set_sample_density, adaptive.hpp): the density's buffers exist while one is set (`density`), W*H
     // entries each; the maps have one per subpath buffer set, B entries each (they are written and read with the set's pass)
     bool density = false;                // a density is set explicitly: run_chunk takes the mapped kernels
@@ -724,15 +729,21 @@ int launch_finalize(cl2_renderer* r, hipStream_t st) {
     return CL2_OK;
 }
 
-// with error tracking on (r->d_mom allocated) the <true> forms also add every addend's second moments
+// with error tracking on (r->d_mom allocated) the <true> forms also add every addend's second moments; with robust buckets on
+// (r->d_bkt allocated) the <., true> forms also add every addend to its bucket
+#define LAUNCH_ACCUMULATING(kernel, ...)                                                                                          \
+    do {                                                                                                                          \
+        if (r->d_bkt) {                                                                                                           \
+            if (r->d_mom) hipLaunchKernelGGL((kernel<true, true>), dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, __VA_ARGS__);       \
+            else hipLaunchKernelGGL((kernel<false, true>), dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, __VA_ARGS__);               \
+        } else if (r->d_mom) hipLaunchKernelGGL((kernel<true>), dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, __VA_ARGS__);          \
+        else hipLaunchKernelGGL((kernel<false>), dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, __VA_ARGS__);                         \
+    } while (0)
+
 int launch_accumulate(cl2_renderer* r, hipStream_t st) {
     Timed t(r, ST_ACCUMULATE, st);
-    if (r->d_mom)
-        hipLaunchKernelGGL(k_accumulate<true>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->FB, r->streams, r->d_finalized, r->d_sample_w,
-                           r->d_light_image, r->d_uni, r->d_acc, r->d_mom);
-    else
-        hipLaunchKernelGGL(k_accumulate<false>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->FB, r->streams, r->d_finalized, r->d_sample_w,
-                           r->d_light_image, r->d_uni, r->d_acc, (float*)nullptr);
+    LAUNCH_ACCUMULATING(k_accumulate, r->FB, r->streams, r->d_finalized, r->d_sample_w, r->d_light_image, r->d_uni, r->d_acc, r->d_mom,
+                        r->d_bkt, r->bkt_M);
     r->acc_clean = false;
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
@@ -741,19 +752,12 @@ int launch_accumulate(cl2_renderer* r, hipStream_t st) {
 // `mapped`: the pass ran with the density's slot maps, `pass` = its number (adaptive.hpp)
 int launch_finalize_accumulate(cl2_renderer* r, hipStream_t st, bool mapped = false, uint32_t pass = 0) {
     Timed t(r, ST_FINALIZE, st);
-    if (mapped) {
-        if (r->d_mom)
-            hipLaunchKernelGGL(k_finalize_accumulate_mapped<true>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
-                               r->d_light_image, r->d_uni, r->d_acc, r->d_mom, r->d_dens_C, r->d_dens_invm, pass, r->d_cam_count);
-        else
-            hipLaunchKernelGGL(k_finalize_accumulate_mapped<false>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
-                               r->d_light_image, r->d_uni, r->d_acc, (float*)nullptr, r->d_dens_C, r->d_dens_invm, pass, r->d_cam_count);
-    } else if (r->d_mom)
-        hipLaunchKernelGGL(k_finalize_accumulate<true>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
-                           r->d_light_image, r->d_uni, r->d_acc, r->d_mom);
+    if (mapped)
+        LAUNCH_ACCUMULATING(k_finalize_accumulate_mapped, r->B, r->W, r->H, r->d_agg, r->d_light_image, r->d_uni, r->d_acc, r->d_mom,
+                            r->d_dens_C, r->d_dens_invm, pass, r->d_cam_count, r->d_bkt, r->bkt_M);
     else
-        hipLaunchKernelGGL(k_finalize_accumulate<false>, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->d_agg,
-                           r->d_light_image, r->d_uni, r->d_acc, (float*)nullptr);
+        LAUNCH_ACCUMULATING(k_finalize_accumulate, r->B, r->W, r->H, r->d_agg, r->d_light_image, r->d_uni, r->d_acc, r->d_mom, r->d_bkt,
+                            r->bkt_M);
     r->acc_clean = false;
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
@@ -1304,9 +1308,11 @@ int cl2_reset_accumulators(cl2_renderer* r) {
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     HIP_TRY(r, hipMemset(r->d_acc, 0, 8 * (size_t)r->FB * sizeof(float)));
     if (r->d_mom) HIP_TRY(r, hipMemset(r->d_mom, 0, 8 * (size_t)r->FB * sizeof(float)));
+    if (r->d_bkt) HIP_TRY(r, hipMemset(r->d_bkt, 0, 4 * (size_t)r->bkt_M * (size_t)r->FB * sizeof(float)));
     if (r->d_cam_count) HIP_TRY(r, hipMemset(r->d_cam_count, 0, (size_t)r->FB * sizeof(unsigned)));
     r->cam_uniform = 0;
     r->mom_valid = r->d_mom != nullptr;
+    r->bkt_valid = r->d_bkt != nullptr;
     r->acc_clean = true;
     r->samples = 0;
     return CL2_OK;
@@ -1325,6 +1331,7 @@ int cl2_write_accumulators_packed(cl2_renderer* r, const float* src, size_t n) {
     TRY(acc_copy(r, r ? r->d_acc : nullptr, src, n, hipMemcpyHostToDevice));
     r->acc_clean = false;
     r->mom_valid = false;                // until cl2_write_moments_packed brings the moments that go with these sums
+    r->bkt_valid = false;                // ... and cl2_write_buckets_packed the buckets
     return CL2_OK;
 }
 
@@ -1513,10 +1520,13 @@ int cl2_reduce_accumulators(cl2_renderer* r) {
     COMM_HIP_TRY(r, api, hipSetDevice(r->device));
     // error tracking: every rank must issue the same collectives.  One small all-reduce (max over [t, -t]: the largest and the
     // smallest t of the ranks) first, t = 0 tracking off, 1 on with invalid moments, 2 on with valid ones
+    // robust buckets: the same for M (0 off) and for their validity (1 valid); they are reduced when M is the same > 0 everywhere
     const double t = r->d_mom ? (r->mom_valid ? 2.0 : 1.0) : 0.0;
-    double tt[2] = {t, -t};
-    TRY(cl2_comm_allreduce_f64(r, tt, 2, 1));
-    const double t_max = tt[0], t_min = -tt[1];
+    const double bm = r->d_bkt ? (double)r->bkt_M : 0.0, bv = r->d_bkt && r->bkt_valid ? 1.0 : 0.0;
+    double tt[6] = {t, -t, bm, -bm, bv, -bv};
+    TRY(cl2_comm_allreduce_f64(r, tt, 6, 1));
+    const double t_max = tt[0], t_min = -tt[1], bm_max = tt[2], bm_min = -tt[3], bv_min = -tt[5];
+    const bool bkt_agree = bm_min == bm_max;
     {
         const int rc = drain(r);
         if (rc != CL2_OK) { r->comm_poisoned = true; comm_abort(r, api); return rc; }
@@ -1524,9 +1534,15 @@ int cl2_reduce_accumulators(cl2_renderer* r) {
     COMM_RCCL_TRY(r, api, api->AllReduce(r->d_acc, r->d_acc, 8 * (size_t)r->FB, ncclFloat, ncclSum, r->comm, r->stream));
     if (t_min >= 1.0)
         COMM_RCCL_TRY(r, api, api->AllReduce(r->d_mom, r->d_mom, 8 * (size_t)r->FB, ncclFloat, ncclSum, r->comm, r->stream));
+    if (bkt_agree && bm_min >= 1.0)
+        COMM_RCCL_TRY(r, api, api->AllReduce(r->d_bkt, r->d_bkt, 4 * (size_t)r->bkt_M * (size_t)r->FB, ncclFloat, ncclSum, r->comm, r->stream));
     TRY(comm_wait(r, api, "cl2_reduce_accumulators"));
     r->acc_clean = false;
     r->mom_valid = t_min == 2.0;
+    r->bkt_valid = bkt_agree && bm_min >= 1.0 && bv_min == 1.0;
+    if (!bkt_agree)
+        return fail(r, CL2_E_STATE, "the robust buckets are off on some ranks or differ in M: the accumulators were reduced, the buckets "
+                                    "are invalid on every rank (cl2_reset_accumulators makes them valid again)");
     if (t_min == 0.0 && t_max >= 1.0)
         return fail(r, CL2_E_STATE, "error tracking is on on some ranks and off on others: the accumulators were reduced, the moments "
                                     "are invalid on every rank (cl2_reset_accumulators makes them valid again)");
@@ -2238,6 +2254,76 @@ int cl2_read_standard_error(cl2_renderer* r, float* out, size_t n_floats) {
     if (rc == CL2_OK && hipStreamSynchronize(r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "k_standard_error failed");
     if (rc == CL2_OK && hipMemcpy(out, d, n_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(r, CL2_E_HIP, "standard error download failed");
+    (void)hipFree(d);
+    return rc;
+}
+
+// ---------------------------------------------------------------- robust picture (csrc/robust.hpp)
+int cl2_set_robust_buckets(cl2_renderer* r, int M) {
+    if (!r) return CL2_E_INVALID;
+    if (M != 0 && (M < ROBUST_MIN_BUCKETS || M > ROBUST_MAX_BUCKETS)) return fail(r, CL2_E_INVALID, "robust buckets: 0 off, 3..16 on");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    if (M == r->bkt_M) return CL2_OK;
+    dev_free(r, r->d_bkt);                                       // off, or another M: the sums of the old buckets mean nothing
+    r->bkt_M = 0;
+    r->bkt_valid = false;
+    if (M == 0) return CL2_OK;
+    const size_t n = 4 * (size_t)M * (size_t)r->FB;
+    TRY(dev_alloc(r, &r->d_bkt, n));
+    HIP_TRY(r, hipMemset(r->d_bkt, 0, n * sizeof(float)));
+    r->bkt_M = M;
+    r->bkt_valid = r->acc_clean;
+    return CL2_OK;
+}
+
+int cl2_get_robust_buckets(const cl2_renderer* r) { return r ? r->bkt_M : CL2_E_INVALID; }
+
+int cl2_read_buckets_packed(cl2_renderer* r, float* dst, size_t n_floats) {
+    if (!r || !dst) return CL2_E_INVALID;
+    if (!r->d_bkt) return fail(r, CL2_E_STATE, "the robust buckets are off (cl2_set_robust_buckets)");
+    if (n_floats != 4 * (size_t)r->bkt_M * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed buckets hold 4*M*W*H floats");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(dst, r->d_bkt, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+
+int cl2_write_buckets_packed(cl2_renderer* r, const float* src, size_t n_floats) {
+    if (!r || !src) return CL2_E_INVALID;
+    if (!r->d_bkt) return fail(r, CL2_E_STATE, "the robust buckets are off (cl2_set_robust_buckets)");
+    if (n_floats != 4 * (size_t)r->bkt_M * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed buckets hold 4*M*W*H floats");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(r->d_bkt, src, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    r->bkt_valid = true;
+    return CL2_OK;
+}
+
+int cl2_robust_picture(cl2_renderer* r, float* out_bgr, size_t n_floats, float* out_stats, size_t n_stats) {
+    if (!r || !out_bgr) return CL2_E_INVALID;
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "the robust picture holds 3*W*H floats");
+    if (out_stats ? n_stats != 2 * (size_t)r->FB : n_stats != 0)
+        return fail(r, CL2_E_INVALID, "the robust statistics hold 2*W*H floats (or are NULL with n_stats 0)");
+    if (!r->d_bkt) return fail(r, CL2_E_STATE, "the robust buckets are off (cl2_set_robust_buckets)");
+    if (!r->bkt_valid)
+        return fail(r, CL2_E_STATE, "the buckets do not cover every sample in the accumulators (they were switched on or resized after "
+                                    "samples, or accumulators were written without their buckets): cl2_reset_accumulators or "
+                                    "cl2_write_buckets_packed");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    const size_t FB = (size_t)r->FB;
+    float* d = nullptr;
+    HIP_TRY(r, hipMalloc(&d, (5 * FB + 1) * sizeof(float)));
+    float2* d_stats = out_stats ? reinterpret_cast<float2*>(d + 3 * FB + (FB & 1)) : nullptr;   // 8-byte aligned: 3 FB + (FB & 1) is even
+    hipLaunchKernelGGL(k_robust_picture, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, r->stream, FB, r->bkt_M, (const float*)r->d_bkt,
+                       d, d_stats);
+    int rc = hipGetLastError() == hipSuccess ? CL2_OK : fail(r, CL2_E_HIP, "k_robust_picture launch failed");
+    if (rc == CL2_OK && hipStreamSynchronize(r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "k_robust_picture failed");
+    if (rc == CL2_OK && hipMemcpy(out_bgr, d, n_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(r, CL2_E_HIP, "robust picture download failed");
+    if (rc == CL2_OK && out_stats && hipMemcpy(out_stats, d_stats, n_stats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(r, CL2_E_HIP, "robust statistics download failed");
     (void)hipFree(d);
     return rc;
 }

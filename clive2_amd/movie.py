@@ -60,6 +60,10 @@ def main(argv=None):
                          "(adaptive sampling, DESIGN.md 6.5)")
     ap.add_argument("--uniform-share", type=float, default=None,
                     help=f"share of the density that stays uniform under --adaptive, in (0, 1] (default {UNIFORM_SHARE})")
+    ap.add_argument("--robust", type=int, nargs="?", const=8, default=0, metavar="M",
+                    help="save the firefly-robust picture: a Gini-trimmed median of means over M buckets per pixel, 3..16 "
+                         "(Renderer.robust_image, DESIGN.md 6.7; default 8; tone-mapped on the host).  Goes with --target-error and "
+                         "--adaptive (the error metric stays on the plain estimates), not with --denoise")
     args = ap.parse_args(argv)
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
         ap.error("--target-error must be positive and finite")
@@ -71,6 +75,10 @@ def main(argv=None):
         ap.error("--adaptive needs --target-error")
     if args.variance_guided and not args.denoise:
         ap.error("--variance-guided needs --denoise")
+    if args.robust and not (3 <= args.robust <= 16):
+        ap.error("--robust takes 3..16 buckets")
+    if args.robust and args.denoise:
+        ap.error("--robust does not go with --denoise: the denoisers take the plain picture")
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
 
@@ -94,6 +102,8 @@ def main(argv=None):
         note = ""
         if args.variance_guided:
             renderer.set_error_tracking(True)
+        if args.robust:
+            renderer.set_robust_buckets(args.robust)
         if args.target_error is not None:
             _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every,
                                                adaptive=args.adaptive, uniform_share=args.uniform_share)
@@ -101,7 +111,9 @@ def main(argv=None):
         else:
             renderer.run_samples(args.samples)
         # a frame leaves the device tone-mapped (6 MB at 1080p; Renderer.image reads 66 MB of accumulators and maps them with numpy)
-        if args.denoise:
+        if args.robust:
+            image = renderer.robust_image
+        elif args.denoise:
             renderer.render_features(args.feature_samples)
             image = renderer.guided_image if args.variance_guided else renderer.denoised_image
         else:

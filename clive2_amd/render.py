@@ -5,6 +5,7 @@ instead of opening a cv2 window (display code is out of scope).
     python -m clive2_amd.render --scene empty --samples 4 --denoise --out cornell_denoised.png
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --error-out err.npy
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --denoise --variance-guided --out cornell_guided.png
+    python -m clive2_amd.render --scene empty --samples 256 --robust --out cornell_robust.png
 
 Several GPUs: start one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE in the environment (e.g.
 `python -m torch.distributed.run --nproc-per-node N -m clive2_amd.render ...`; any spawner will do, torch
@@ -59,6 +60,10 @@ def main(argv=None):
                     help=f"share of the density that stays uniform under --adaptive, in (0, 1] (default {UNIFORM_SHARE})")
     ap.add_argument("--error-out", type=str, default=None,
                     help="save the per-pixel standard error (Renderer.standard_error: (H, W, 4) float32 b, g, r, luma) as .npy")
+    ap.add_argument("--robust", type=int, nargs="?", const=8, default=0, metavar="M",
+                    help="save the firefly-robust picture: a Gini-trimmed median of means over M buckets per pixel, 3..16 "
+                         "(Renderer.robust_image, DESIGN.md 6.7; default 8; tone-mapped on the host).  Goes with --target-error and "
+                         "--adaptive (the error metric stays on the plain estimates), not with --denoise")
     args = ap.parse_args(argv)
     # refused before any renderer is made
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
@@ -71,6 +76,10 @@ def main(argv=None):
         ap.error("--adaptive needs --target-error")
     if args.variance_guided and not args.denoise:
         ap.error("--variance-guided needs --denoise")
+    if args.robust and not (3 <= args.robust <= 16):
+        ap.error("--robust takes 3..16 buckets")
+    if args.robust and args.denoise:
+        ap.error("--robust does not go with --denoise: the denoisers take the plain picture")
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
 
@@ -89,6 +98,8 @@ def main(argv=None):
         renderer.set_reproducible(True)
     if args.target_error is not None or args.error_out or args.variance_guided:
         renderer.set_error_tracking(True)
+    if args.robust:
+        renderer.set_robust_buckets(args.robust)
     # seed buffers of the job: stream k of rank r is buffer r * K + k
     renderer.set_seeds(stream_seeds(args.width * args.height, K, first_rank=rank * K))
     if world > 1:
@@ -136,7 +147,9 @@ def main(argv=None):
     # Tone-mapped uint8, BGR.  The film sits BEHIND the pinhole, so the picture on it is already upright
     # when read row 0 first (row 0 looks up at the ceiling light): the reference hands `renderer.image`
     # to cv2 unflipped (render.py:35-37).  Only the channel order changes for a PNG (BGR -> RGB).
-    if args.denoise:
+    if args.robust:
+        image = renderer.robust_image
+    elif args.denoise:
         t1 = time.time()
         renderer.render_features(args.feature_samples)
         image = renderer.guided_image if args.variance_guided else renderer.denoised_image

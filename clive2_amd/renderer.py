@@ -634,6 +634,53 @@ class Renderer:
         self._check(self._L.cl2_read_camera_samples(self._h, ptr(out), C.c_size_t(out.size)), "cl2_read_camera_samples")
         return out
 
+    # ---- robust picture (cl2_set_robust_buckets ... cl2_robust_picture, csrc/robust.hpp) ----
+    ROBUST_BUCKETS = 8
+
+    def set_robust_buckets(self, M=ROBUST_BUCKETS):
+        """Keep M partial sums per pixel (3..16; 0 = off, the default; 16*M*W*H bytes of device memory while on): every addend of
+        a pixel goes to bucket (addends so far) % M.  Switched on, or to another M, while the accumulators hold samples, the
+        buckets stay invalid -- and robust_radiance() refuses -- until reset_accumulators()."""
+        M = int(M)
+        if M != 0 and not (3 <= M <= 16):
+            raise ValueError("robust buckets: M must be 0 (off) or in 3..16")
+        self._check(self._L.cl2_set_robust_buckets(self._h, M), "cl2_set_robust_buckets")
+
+    @property
+    def robust_buckets(self):
+        """M, 0 while the buckets are off"""
+        return int(self._L.cl2_get_robust_buckets(self._h))
+
+    def buckets(self):
+        """The bucket buffer [M][4][W*H] float32 (bucket k: rows b, g, r, w), flat."""
+        a = np.empty(4 * max(self.robust_buckets, 1) * self.batch_size, np.float32)
+        self._check(self._L.cl2_read_buckets_packed(self._h, ptr(a), C.c_size_t(a.size)), "cl2_read_buckets_packed")
+        return a
+
+    def load_buckets(self, a):
+        """Write the bucket buffer (checkpoints: after load_packed_accumulators, which invalidates the buckets)."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        M = self.robust_buckets
+        if M and a.size != 4 * M * self.batch_size:
+            raise ValueError(f"the buckets hold 4*M*W*H = {4 * M * self.batch_size} floats, got {a.size}")
+        self._check(self._L.cl2_write_buckets_packed(self._h, ptr(a), C.c_size_t(a.size)), "cl2_write_buckets_packed")
+
+    def robust_radiance(self, return_stats=False):
+        """`radiance` as a Gini-trimmed median of means over the buckets (set_robust_buckets() before the samples): float32
+        (H,W,3), BGR.  Where a pixel's bucket means agree it is `radiance` up to the order of the float32 sums; a bucket that holds
+        a firefly is left out.  return_stats=True returns (picture, stats): stats (H,W,2) float32 = the Gini coefficient of the
+        pixel's bucket means and the number of buckets trimmed at either end."""
+        out = np.empty((self.pixel_height, self.pixel_width, 3), np.float32)
+        st = np.empty((self.pixel_height, self.pixel_width, 2), np.float32) if return_stats else None
+        self._check(self._L.cl2_robust_picture(self._h, ptr(out), C.c_size_t(out.size), ptr(st), C.c_size_t(0 if st is None else st.size)),
+                    "cl2_robust_picture")
+        return (out, st) if return_stats else out
+
+    @property
+    def robust_image(self):
+        """`image` of the robust radiance: tone_map(robust_radiance(), exposure=4.0) on the host, uint8 (H,W,3), BGR."""
+        return tone_map(self.robust_radiance(), exposure=4.0)
+
     def probe_math(self, which, x):
         """Device detmath / exact-reciprocal functions on a float32 array (`which`: sin cos acos atan exp asin rcp div_pi)."""
         code = ["sin", "cos", "acos", "atan", "exp", "asin", "rcp", "div_pi"].index(which)

@@ -215,7 +215,11 @@ int cl2_comm_init_rank(cl2_renderer* r, int nranks, int rank, const void* unique
  * different collectives, the call first all-reduces every rank's tracking state (cl2_comm_allreduce_f64, op max over [t, -t]):
  * one small collective more than the accumulators' all-reduce, whether tracking is on or not.  If tracking is on on some ranks
  * and off on others, the accumulators are reduced as usual, the moments are marked invalid everywhere and the call returns
- * CL2_E_STATE; moments invalid on any rank are invalid on every rank after the sum. */
+ * CL2_E_STATE; moments invalid on any rank are invalid on every rank after the sum.
+ * The robust buckets (cl2_set_robust_buckets) ride on the same handshake: when every rank has them on with the same M the bucket
+ * buffer is reduced too (bucket k of the job = the sum of the ranks' buckets k: independent samples, the same estimator), and the
+ * result is valid if it was valid on every rank.  If the ranks disagree (off on some, or another M), what is reduced without
+ * buckets is reduced, the buckets are marked invalid on every rank and the call returns CL2_E_STATE. */
 int cl2_reduce_accumulators(cl2_renderer* r);
 /* n <= 16 host doubles, in place, op 0 = sum, 1 = max over the ranks: barrier, max-over-ranks clock,
  * whole-job ray tally, error-flag agreement before the collective */
@@ -497,6 +501,40 @@ int cl2_set_adaptive_sampling(cl2_renderer* r, int on, double uniform_share);
 int cl2_get_adaptive_sampling(const cl2_renderer* r);
 /* camera samples each pixel received since the last cl2_reset_accumulators (one per stream and pass without a density) */
 int cl2_read_camera_samples(cl2_renderer* r, float* out, size_t n);
+
+/* -- robust picture: a Gini-trimmed median of means over per-pixel buckets (csrc/robust.hpp).  No reference
+ *    counterpart.
+ *
+ * While the buckets are on, a buffer bkt [M][4][W*H] of float32 sums (bucket k: rows b, g, r, w) gets every addend (x_0, x_1, x_2,
+ * w) of the error estimates' definition above: bucket k = (int)a7 % M with a7 = the pixel's accumulator row 7 before the addend,
+ * rows 4k + c += x_c and 4k + 3 += w, one float32 add each, in stream order.  Accumulators and moments get the bytes they get
+ * without buckets.  The picture, per pixel, in float64 from the float32 sums, every operation in the order written:
+ *     bucket k is valid iff W_k > 0 and W_k < +inf;  m = valid buckets;  m = 0: the pixel is 0, 0, 0
+ *     key_k = (I_b 0.0722f + I_g 0.7152f) + I_r 0.2126f with I_c = X_ck / W_k;  a NaN key counts as +inf
+ *     rank the valid buckets by key ascending, equal keys in bucket order
+ *     over the ranks j = 1 .. m:  v_j = key > 0 ? key : 0,  S += v_j,  N += (2j - m - 1) v_j
+ *     G = 1 if S is NaN or +inf, 0 if !(S > 0), else N / (m S) (0 if !(G > 0), 1 if G > 1)         -- the Gini coefficient
+ *     c = min(floor(G m / 2), (m - 1) / 2) (integer division);  kept = ranks c+1 .. m-c
+ *     X_c, W = float32 sums over the kept buckets in ascending bucket index;  pixel = scrub(X_c / W) in float32, BGR
+ * Where the bucket means agree nothing is trimmed and the pixel is the plain ratio estimator; a bucket that holds a firefly is
+ * dropped, with the smallest one.
+ *
+ * Off by default; with it off every kernel runs exactly the code it runs without this feature.  M = 0 switches off and frees the
+ * buffer; M = 3 .. 16 switches on (16 M W H bytes of device memory: 265 MB at 1080p with M = 8), zeroed; another M than the
+ * current one frees, allocates and zeroes; anything else is CL2_E_INVALID.  The buckets are VALID when every addend in the
+ * accumulators also went into them, by the rules of the moments: valid when switched on (or resized) over clean accumulators,
+ * after cl2_reset_accumulators (which zeroes them) and after cl2_write_buckets_packed; invalid when switched on or resized over
+ * accumulators that hold sums and after cl2_write_accumulators_packed. -- */
+int cl2_set_robust_buckets(cl2_renderer* r, int M);
+int cl2_get_robust_buckets(const cl2_renderer* r);               /* M, 0 = off */
+/* the bucket buffer [M][4][W*H] as host floats, for checkpoints and tests (n_floats = 4*M*W*H, else CL2_E_INVALID); CL2_E_STATE
+ * with the buckets off; reading works on invalid buckets too, writing makes them valid */
+int cl2_read_buckets_packed(cl2_renderer* r, float* host_dst, size_t n_floats);
+int cl2_write_buckets_packed(cl2_renderer* r, const float* host_src, size_t n_floats);
+/* out_bgr: (H, W, 3) float32, n_floats = 3*W*H.  out_stats: NULL (n_stats = 0) or (H, W, 2) float32 (n_stats = 2*W*H) that
+ * receive (float)G and (float)c per pixel.  CL2_E_STATE with the buckets off or invalid (the message says how to make them
+ * valid).  Touches neither seeds, accumulators, moments, buckets nor counters. */
+int cl2_robust_picture(cl2_renderer* r, float* out_bgr, size_t n_floats, float* out_stats, size_t n_stats);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COUNTERS = ("SQ_INSTS_VALU", "TCP_TOTAL_CACHE_ACCESSES_sum")
 # r08: the accumulate kernels became templates on MOMENTS; the render runs the <false> instantiations
 # r11: the camera-ray generator and the resolve kernel gained a MAPPED parameter (adaptive sampling); the render runs <false>
+# r14: the accumulate kernels gained a BUCKETS parameter (robust picture); the render runs <false,false>
 RENAMED = {"k_finalize_accumulate": "k_finalize_accumulate<false>", "k_accumulate": "k_accumulate<false>",
+           "k_finalize_accumulate<false>": "k_finalize_accumulate<false,false>", "k_accumulate<false>": "k_accumulate<false,false>",
            "k_gen_rays": "k_gen_rays<false>", "k_gen_camera_rays": "k_gen_camera_rays<false>",
            **{f"k_connect_resolve<{a}>": f"k_connect_resolve<{a},false>"
               for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true")}}
