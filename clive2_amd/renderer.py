@@ -231,21 +231,33 @@ class Renderer:
 
     _PICTURES = {"image": 0, "unweighted_image": 1, "unidirectional_image": 2}
 
-    def tone_mapped(self, which="image", exposure=4.0, white_point=1.0):
+    def tone_log_sum(self, which="image"):
+        """Sum over the pixels of log(0.1 + luma) of one of the three pictures, in float64, computed on the device
+        (cl2_tone_log_sum): what `tone_mapped()` forms Lw = exp(sum / (W*H)) from.  NaN where a pixel's luma is below -0.1."""
+        s = C.c_double(0.0)
+        self._check(self._L.cl2_tone_log_sum(self._h, self._PICTURES[which], C.byref(s)), "cl2_tone_log_sum")
+        return float(s.value)
+
+    def tone_mapped(self, which="image", exposure=4.0, white_point=1.0, log_average=None):
         """`tone_map` (camera.py:73-82) of one of the three pictures of renderer.py:293-316, computed ON THE DEVICE from
         the accumulators (cl2_tone_log_sum + cl2_tone_map, csrc/tonemap.hpp): uint8 (H,W,3), BGR.  Only the 3*W*H bytes
         of the picture cross PCIe (the host path reads the 32*W*H bytes of the accumulators and maps them with numpy).
-        Same arithmetic and dtypes as the host path; the float64 log-luminance sum is added in another order, so a byte
-        can differ from `.image` where 255*x/(x+w) lies within ~1e-13 of an integer."""
+        Same arithmetic and dtypes as the host path: given the same Lw the bytes are the host's, every one (tests/test_gpu_tone.py).
+        The float64 log-luminance sum is added in another order, so Lw can differ from the host's in its last bits, and a byte can
+        then differ from `.image` by one count where 255*x/(x+w) lies within ~1e-13 (relative) of an integer.  Among ordinary
+        pixels that is rare; a saturated pixel (x > 2^53, so x + w == x) always sits there: fl(255*x)/x is 255 or the double
+        below it by the last bits of x, so many such bytes trade 254 for 255 at once (tests/tone_reference.py: fragile).
+        `log_average`: use this Lw instead of the picture's own (no log-sum launch)."""
         w = self._PICTURES[which]
         # the device arithmetic restates what numpy >= 2 (NEP 50 promotion) makes of camera.py:73-82: the float32 picture times
         # the exposure stays float32 and is widened by the division by the float64 Lw.  numpy 1.x keeps `result` in float32
         # (value-based casting), and the host path then differs from this one by far more than one count (ADVICE r3).
         if int(np.__version__.split(".")[0]) < 2:
             raise RendererError("tone_mapped() reproduces the reference's tone map under numpy >= 2 (NEP 50) only; use .image")
-        s = C.c_double(0.0)
-        self._check(self._L.cl2_tone_log_sum(self._h, w, C.byref(s)), "cl2_tone_log_sum")
-        log_avg = np.exp(np.float64(s.value) / (self.pixel_height * self.pixel_width))       # Lw, with numpy's exp
+        if log_average is None:
+            log_avg = np.exp(np.float64(self.tone_log_sum(which)) / (self.pixel_height * self.pixel_width))   # Lw, with numpy's exp
+        else:
+            log_avg = log_average
         out = np.empty((self.pixel_height, self.pixel_width, 3), np.uint8)
         self._check(self._L.cl2_tone_map(self._h, w, float(exposure), float(white_point), float(log_avg), ptr(out),
                                          C.c_size_t(out.size)), "cl2_tone_map")

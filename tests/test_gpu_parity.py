@@ -584,7 +584,9 @@ def test_device_tone_map_matches_reference_fixture_and_host_path(cornell_small):
     `tone_map` made of the fixture's accumulators (tests/golden/renderer_glue.npz: NaN / +-inf / zero-weight entries
     included) and (b) the host path `Renderer.image` on a real render.  Same arithmetic and numpy dtypes; the float64
     log-luminance sum is added in another order than numpy's pairwise sum, so Lw may differ in its last bits and a byte
-    may move where 255*x/(x+w) lies within ~1e-13 of an integer: at most one count, in at most 2 bytes per picture."""
+    may move where 255*x/(x+w) lies within ~1e-13 of an integer: at most one count, in at most 2 bytes per picture.
+    (The 2 bytes hold for these two inputs, not in general: a saturated pixel, x > 2^53, always sits on such an integer and
+    trades 254 for 255 with the last bit of Lw.  tests/test_gpu_tone.py compares bit for bit, given Lw, and names those bytes.)"""
     import os
     import clive2_amd as c2
     from clive2_amd.renderer import Renderer, make_seeds
