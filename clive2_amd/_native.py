@@ -94,6 +94,7 @@ EXPORTS = [
     "cl2_set_sample_density", "cl2_read_sample_density", "cl2_update_sample_density", "cl2_set_adaptive_sampling",
     "cl2_get_adaptive_sampling", "cl2_read_camera_samples",
     "cl2_set_robust_buckets", "cl2_get_robust_buckets", "cl2_read_buckets_packed", "cl2_write_buckets_packed", "cl2_robust_picture",
+    "cl2_denoise_robust",
 ]
 
 
@@ -184,6 +185,8 @@ def lib(variant=None):
         L.cl2_read_buckets_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.cl2_write_buckets_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.cl2_robust_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        L.cl2_denoise_robust.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_size_t]
         for name in ("cl2_reduce_accumulators", "cl2_comm_destroy", "cl2_comm_abort", "cl2_synchronize"):
             getattr(L, name).argtypes = [C.c_void_p]
         _libs[variant] = L

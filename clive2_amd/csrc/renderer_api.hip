@@ -22,6 +22,7 @@
 #include "kernels.hpp"
 #include "denoise.hpp"
 #include "denoise_guided.hpp"
+#include "denoise_robust.hpp"
 #include "error_estimate.hpp"
 #include "adaptive.hpp"
 #include "tonemap.hpp"
@@ -2349,6 +2350,54 @@ int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float 
     float* const dvar = out_var ? r->d_dn_var : nullptr;
     hipLaunchKernelGGL(k_denoise_guided_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc,
                        (const float*)r->d_mom, r->d_dn[0], iterations == 0 ? r->d_dn_out : (float*)nullptr, dvar);
+    HIP_TRY(r, hipGetLastError());
+    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
+    const float den_a = sigma_albedo * sigma_albedo;
+    for (int i = 0; i < iterations; i++) {
+        const int step = 1 << i;
+        const float4* cin = r->d_dn[i & 1];
+        float4* cout = r->d_dn[(i + 1) & 1];
+        float* out3 = i == iterations - 1 ? r->d_dn_out : nullptr;
+        if (step == 1)
+            hipLaunchKernelGGL(k_denoise_guided_pass<1>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        else if (step == 2)
+            hipLaunchKernelGGL(k_denoise_guided_pass<2>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        else
+            hipLaunchKernelGGL(k_denoise_guided_pass<0>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        HIP_TRY(r, hipGetLastError());
+    }
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(out_bgr, r->d_dn_out, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_var) HIP_TRY(r, hipMemcpy(out_var, r->d_dn_var, n_var * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+
+// The guided filter on the robust picture (denoise_robust.hpp): colour and guide variance from the kept buckets, then
+// cl2_denoise_guided's passes.  Reads the buckets and the features only.
+int cl2_denoise_robust(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
+                       size_t n_floats, float* out_var, size_t n_var) {
+    STAGE_PROLOGUE(r);
+    if (!out_bgr) return fail(r, CL2_E_INVALID, "NULL output");
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "denoised picture must hold 3*W*H floats");
+    if (out_var ? n_var != (size_t)r->FB : n_var != 0)
+        return fail(r, CL2_E_INVALID, "guide variance must hold W*H floats (or be NULL with n_var 0)");
+    if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
+    auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
+    if (bad(sigma_luma) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
+    if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
+    if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
+    if (!r->d_bkt) return fail(r, CL2_E_STATE, "the robust buckets are off (cl2_set_robust_buckets)");
+    if (!r->bkt_valid)
+        return fail(r, CL2_E_STATE, "the buckets do not cover every sample in the accumulators (they were switched on or resized after "
+                                    "samples, or accumulators were written without their buckets): cl2_reset_accumulators or "
+                                    "cl2_write_buckets_packed");
+    const size_t FB = (size_t)r->FB;
+    TRY(need_filter_buffers(r));
+    if (!r->d_dn_var) TRY(dev_alloc(r, &r->d_dn_var, FB));
+    hipStream_t st = r->stream;
+    float* const dvar = out_var ? r->d_dn_var : nullptr;
+    hipLaunchKernelGGL(k_denoise_robust_input, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, st, FB, r->bkt_M, (const float*)r->d_bkt,
+                       r->d_dn[0], iterations == 0 ? r->d_dn_out : (float*)nullptr, dvar);
     HIP_TRY(r, hipGetLastError());
     const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
     const float den_a = sigma_albedo * sigma_albedo;

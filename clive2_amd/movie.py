@@ -64,6 +64,11 @@ def main(argv=None):
                     help="save the firefly-robust picture: a Gini-trimmed median of means over M buckets per pixel, 3..16 "
                          "(Renderer.robust_image, DESIGN.md 6.7; default 8; tone-mapped on the host).  Goes with --target-error and "
                          "--adaptive (the error metric stays on the plain estimates), not with --denoise")
+    ap.add_argument("--robust-denoise", type=int, nargs="?", const=8, default=0, metavar="M",
+                    help="save the robust picture after the variance-guided filter, guided by the variance of the buckets the trim "
+                         "kept (Renderer.robust_guided_image, DESIGN.md 6.8): M buckets per pixel, 3..16, default 8; the feature pass "
+                         "takes --feature-samples; tone-mapped on the host.  Goes with --target-error and --adaptive (the error "
+                         "metric stays on the plain estimates), not with --robust, --denoise or --variance-guided")
     args = ap.parse_args(argv)
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
         ap.error("--target-error must be positive and finite")
@@ -79,6 +84,10 @@ def main(argv=None):
         ap.error("--robust takes 3..16 buckets")
     if args.robust and args.denoise:
         ap.error("--robust does not go with --denoise: the denoisers take the plain picture")
+    if args.robust_denoise and not (3 <= args.robust_denoise <= 16):
+        ap.error("--robust-denoise takes 3..16 buckets")
+    if args.robust_denoise and (args.robust or args.denoise or args.variance_guided):
+        ap.error("--robust-denoise is a picture of its own: it does not go with --robust, --denoise or --variance-guided")
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
 
@@ -102,8 +111,8 @@ def main(argv=None):
         note = ""
         if args.variance_guided:
             renderer.set_error_tracking(True)
-        if args.robust:
-            renderer.set_robust_buckets(args.robust)
+        if args.robust or args.robust_denoise:
+            renderer.set_robust_buckets(args.robust or args.robust_denoise)
         if args.target_error is not None:
             _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every,
                                                adaptive=args.adaptive, uniform_share=args.uniform_share)
@@ -113,6 +122,9 @@ def main(argv=None):
         # a frame leaves the device tone-mapped (6 MB at 1080p; Renderer.image reads 66 MB of accumulators and maps them with numpy)
         if args.robust:
             image = renderer.robust_image
+        elif args.robust_denoise:
+            renderer.render_features(args.feature_samples)
+            image = renderer.robust_guided_image
         elif args.denoise:
             renderer.render_features(args.feature_samples)
             image = renderer.guided_image if args.variance_guided else renderer.denoised_image

@@ -6,6 +6,7 @@ instead of opening a cv2 window (display code is out of scope).
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --error-out err.npy
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --denoise --variance-guided --out cornell_guided.png
     python -m clive2_amd.render --scene empty --samples 256 --robust --out cornell_robust.png
+    python -m clive2_amd.render --scene empty --samples 256 --robust-denoise --out cornell_robust_denoised.png
 
 Several GPUs: start one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE in the environment (e.g.
 `python -m torch.distributed.run --nproc-per-node N -m clive2_amd.render ...`; any spawner will do, torch
@@ -64,6 +65,11 @@ def main(argv=None):
                     help="save the firefly-robust picture: a Gini-trimmed median of means over M buckets per pixel, 3..16 "
                          "(Renderer.robust_image, DESIGN.md 6.7; default 8; tone-mapped on the host).  Goes with --target-error and "
                          "--adaptive (the error metric stays on the plain estimates), not with --denoise")
+    ap.add_argument("--robust-denoise", type=int, nargs="?", const=8, default=0, metavar="M",
+                    help="save the robust picture after the variance-guided filter, guided by the variance of the buckets the trim "
+                         "kept (Renderer.robust_guided_image, DESIGN.md 6.8): M buckets per pixel, 3..16, default 8; the feature pass "
+                         "takes --feature-samples; tone-mapped on the host.  Goes with --target-error and --adaptive (the error "
+                         "metric stays on the plain estimates), not with --robust, --denoise or --variance-guided")
     args = ap.parse_args(argv)
     # refused before any renderer is made
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
@@ -80,6 +86,10 @@ def main(argv=None):
         ap.error("--robust takes 3..16 buckets")
     if args.robust and args.denoise:
         ap.error("--robust does not go with --denoise: the denoisers take the plain picture")
+    if args.robust_denoise and not (3 <= args.robust_denoise <= 16):
+        ap.error("--robust-denoise takes 3..16 buckets")
+    if args.robust_denoise and (args.robust or args.denoise or args.variance_guided):
+        ap.error("--robust-denoise is a picture of its own: it does not go with --robust, --denoise or --variance-guided")
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
 
@@ -98,8 +108,8 @@ def main(argv=None):
         renderer.set_reproducible(True)
     if args.target_error is not None or args.error_out or args.variance_guided:
         renderer.set_error_tracking(True)
-    if args.robust:
-        renderer.set_robust_buckets(args.robust)
+    if args.robust or args.robust_denoise:
+        renderer.set_robust_buckets(args.robust or args.robust_denoise)
     # seed buffers of the job: stream k of rank r is buffer r * K + k
     renderer.set_seeds(stream_seeds(args.width * args.height, K, first_rank=rank * K))
     if world > 1:
@@ -149,6 +159,11 @@ def main(argv=None):
     # to cv2 unflipped (render.py:35-37).  Only the channel order changes for a PNG (BGR -> RGB).
     if args.robust:
         image = renderer.robust_image
+    elif args.robust_denoise:
+        t1 = time.time()
+        renderer.render_features(args.feature_samples)
+        image = renderer.robust_guided_image
+        print(f"[rank {rank}] features ({args.feature_samples} rays per pixel) and denoising took {time.time() - t1:.2f} seconds")
     elif args.denoise:
         t1 = time.time()
         renderer.render_features(args.feature_samples)

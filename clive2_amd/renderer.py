@@ -693,6 +693,32 @@ class Renderer:
         """`image` of the robust radiance: tone_map(robust_radiance(), exposure=4.0) on the host, uint8 (H,W,3), BGR."""
         return tone_map(self.robust_radiance(), exposure=4.0)
 
+    # ---- guided filter on the robust picture (cl2_denoise_robust, csrc/denoise_robust.hpp, DESIGN.md 6.8) ----
+    # GUIDED_DEFAULTS, confirmed by the sweep of tools/robust_denoise_quality.py (DESIGN 6.8)
+    ROBUST_GUIDED_DEFAULTS = dict(iterations=4, sigma_luma=4.0, sigma_depth=0.1, sigma_albedo=0.1)
+
+    def robust_guided_radiance(self, iterations=None, sigma_luma=None, sigma_depth=None, sigma_albedo=None, return_variance=False):
+        """`robust_radiance()` after the variance-guided a-trous filter, its guide the variance of the mean of the buckets the trim
+        kept (set_robust_buckets() before the samples, render_features() first; error tracking is not needed): float32 (H,W,3),
+        BGR.  A trimmed firefly is in neither the colour nor the guide, so the filter does not open for it.  Unset arguments take
+        ROBUST_GUIDED_DEFAULTS; iterations=0 returns robust_radiance() itself.  return_variance=True returns (picture, v'): v'
+        (H,W) float32 is the filter's GUIDE after the last pass, not an error estimate."""
+        d = self.ROBUST_GUIDED_DEFAULTS
+        it = d["iterations"] if iterations is None else int(iterations)
+        sl = d["sigma_luma"] if sigma_luma is None else float(sigma_luma)
+        sd = d["sigma_depth"] if sigma_depth is None else float(sigma_depth)
+        sa = d["sigma_albedo"] if sigma_albedo is None else float(sigma_albedo)
+        out = np.empty((self.pixel_height, self.pixel_width, 3), np.float32)
+        var = np.empty((self.pixel_height, self.pixel_width), np.float32) if return_variance else None
+        self._check(self._L.cl2_denoise_robust(self._h, it, sl, sd, sa, ptr(out), C.c_size_t(out.size), ptr(var),
+                                               C.c_size_t(0 if var is None else var.size)), "cl2_denoise_robust")
+        return (out, var) if return_variance else out
+
+    @property
+    def robust_guided_image(self):
+        """`image` of the filtered robust radiance: tone_map(robust_guided_radiance(), exposure=4.0) on the host, uint8 (H,W,3), BGR."""
+        return tone_map(self.robust_guided_radiance(), exposure=4.0)
+
     def probe_math(self, which, x):
         """Device detmath / exact-reciprocal functions on a float32 array (`which`: sin cos acos atan exp asin rcp div_pi)."""
         code = ["sin", "cos", "acos", "atan", "exp", "asin", "rcp", "div_pi"].index(which)

@@ -535,6 +535,26 @@ int cl2_write_buckets_packed(cl2_renderer* r, const float* host_src, size_t n_fl
  * receive (float)G and (float)c per pixel.  CL2_E_STATE with the buckets off or invalid (the message says how to make them
  * valid).  Touches neither seeds, accumulators, moments, buckets nor counters. */
 int cl2_robust_picture(cl2_renderer* r, float* out_bgr, size_t n_floats, float* out_stats, size_t n_stats);
+/* The variance-guided filter on the robust picture (csrc/denoise_robust.hpp): cl2_denoise_guided's passes, unchanged, on
+ * an input made from the buckets alone.  Per pixel:
+ *     trim      valid, key_k (float64, a NaN key is +inf), ranks, m, G, c and the kept set exactly as stated above
+ *     colour    c = the pixel of cl2_robust_picture, byte for byte (float32 sums over the kept buckets in ascending bucket index,
+ *               divided and scrubbed; 0, 0, 0 at m = 0)
+ *     variance  n = m - 2c, the number of kept buckets;  v = 0 for m = 0;  v = 2^100 for n < 2;  otherwise, in float64 over the kept
+ *               buckets in ascending bucket index:
+ *                   ybar = (sum key_k) / (double)n,   Q = sum (key_k - ybar) (key_k - ybar),   var = (Q / (double)(n - 1)) / (double)n
+ *               v = var < 2^100 ? (float)var : 2^100     (a NaN or inf from a +inf key takes the cap)
+ * v is the between-bucket variance of the mean of the kept bucket lumas: a firefly that was trimmed is in neither c nor v, so the
+ * filter does not open for it.  v ignores that the buckets' weights differ; it is a filter GUIDE, like v' of cl2_denoise_guided,
+ * and nothing may stop on it.
+ * Arguments, outputs and their checks are cl2_denoise_guided's (iterations 0..12, 0 = the input: the robust picture and v; sigmas
+ * positive and finite, sigma_albedo^2 not below FLT_MIN; out_var NULL with n_var 0, or W*H floats; else CL2_E_INVALID).
+ * CL2_E_STATE without current features, with the buckets off or with invalid buckets (cl2_robust_picture's messages).  Error
+ * tracking need not be on: neither accumulators nor moments are read.  Touches neither seeds, accumulators, moments, buckets,
+ * features nor counters; allocates the filters' working buffers only.  Defaults of the Python binding:
+ * Renderer.ROBUST_GUIDED_DEFAULTS. */
+int cl2_denoise_robust(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
+                       size_t n_floats, float* out_var, size_t n_var);
 
 #ifdef __cplusplus
 }
