@@ -95,6 +95,7 @@ EXPORTS = [
     "cl2_get_adaptive_sampling", "cl2_read_camera_samples",
     "cl2_set_robust_buckets", "cl2_get_robust_buckets", "cl2_read_buckets_packed", "cl2_write_buckets_packed", "cl2_robust_picture",
     "cl2_denoise_robust",
+    "cl2_keep_picture", "cl2_kept_picture", "cl2_write_picture", "cl2_read_picture", "cl2_picture_log_sum", "cl2_picture_tone_map",
 ]
 
 
@@ -187,6 +188,12 @@ def lib(variant=None):
         L.cl2_robust_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         L.cl2_denoise_robust.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_size_t]
+        L.cl2_keep_picture.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
+        L.cl2_kept_picture.argtypes = [C.c_void_p]
+        L.cl2_write_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_read_picture.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_picture_log_sum.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.cl2_picture_tone_map.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_size_t]
         for name in ("cl2_reduce_accumulators", "cl2_comm_destroy", "cl2_comm_abort", "cl2_synchronize"):
             getattr(L, name).argtypes = [C.c_void_p]
         _libs[variant] = L

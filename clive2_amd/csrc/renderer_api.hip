@@ -26,6 +26,7 @@
 #include "error_estimate.hpp"
 #include "adaptive.hpp"
 #include "tonemap.hpp"
+#include "tonemap_picture.hpp"
 #include "det_splat.hpp"
 #include "bvh_builder.hpp"
 #include "comm_rccl.hpp"
@@ -120,6 +121,8 @@ struct cl2_renderer {
     float* d_acc = nullptr;            // [8][B]
     double* d_tone_partial = nullptr;  // device tone map: per-workgroup partial sums + the total (allocated by the first call)
     uint8_t* d_tone_out = nullptr;     // device tone map: the uint8 picture before it is copied out
+    float* d_pic = nullptr;            // kept picture (cl2_keep_picture, tonemap_picture.hpp): (H, W, 3) b, g, r, allocated on first use
+    int pic_kind = 0;                  // ... 0 none, 1 denoised, 2 guided, 3 robust, 4 robust-guided, 5 loaded (cl2_write_picture)
     Stats* d_stats = nullptr;
     unsigned long long* d_block_stats = nullptr;   // [grid][4]: rays, box tests, tri tests, counted rays per workgroup slot
 
@@ -2050,11 +2053,10 @@ int need_filter_buffers(cl2_renderer* r) {
 }
 }  // namespace
 
-int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* out_bgr,
-                size_t n_floats) {
-    STAGE_PROLOGUE(r);
-    if (!out_bgr) return fail(r, CL2_E_INVALID, "NULL output");
-    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "denoised picture must hold 3*W*H floats");
+namespace {
+// cl2_denoise after its output checks, shared with cl2_keep_picture: the remaining checks and every launch; the last launch
+// writes the (H, W, 3) picture to `dst` (device memory; nullptr: d_dn_out)
+int run_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* dst) {
     if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
     auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
     if (bad(sigma_color) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
@@ -2065,9 +2067,10 @@ int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
     if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
     const size_t FB = (size_t)r->FB;
     TRY(need_filter_buffers(r));
+    if (!dst) dst = r->d_dn_out;
     hipStream_t st = r->stream;
     hipLaunchKernelGGL(k_denoise_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc, r->d_dn[0],
-                       iterations == 0 ? r->d_dn_out : (float*)nullptr);
+                       iterations == 0 ? dst : (float*)nullptr);
     HIP_TRY(r, hipGetLastError());
     const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
     const float den_a = sigma_albedo * sigma_albedo;
@@ -2076,7 +2079,7 @@ int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
         const float den_c = std::ldexp(sigma_color * sigma_color, -2 * i);      // sigma_color^2 * 4^-i, exact scaling
         const float4* cin = r->d_dn[i & 1];
         float4* cout = r->d_dn[(i + 1) & 1];
-        float* out3 = i == iterations - 1 ? r->d_dn_out : nullptr;
+        float* out3 = i == iterations - 1 ? dst : nullptr;
         if (step == 1)
             hipLaunchKernelGGL(k_denoise_pass<1>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
         else if (step == 2)
@@ -2085,7 +2088,16 @@ int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
             hipLaunchKernelGGL(k_denoise_pass<0>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
         HIP_TRY(r, hipGetLastError());
     }
-    TRY(drain(r));
+    return drain(r);
+}
+}  // namespace
+
+int cl2_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* out_bgr,
+                size_t n_floats) {
+    STAGE_PROLOGUE(r);
+    if (!out_bgr) return fail(r, CL2_E_INVALID, "NULL output");
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "denoised picture must hold 3*W*H floats");
+    TRY(run_denoise(r, iterations, sigma_color, sigma_depth, sigma_albedo, nullptr));
     HIP_TRY(r, hipMemcpy(out_bgr, r->d_dn_out, n_floats * sizeof(float), hipMemcpyDeviceToHost));
     return CL2_OK;
 }
@@ -2301,26 +2313,42 @@ int cl2_write_buckets_packed(cl2_renderer* r, const float* src, size_t n_floats)
     return CL2_OK;
 }
 
-int cl2_robust_picture(cl2_renderer* r, float* out_bgr, size_t n_floats, float* out_stats, size_t n_stats) {
-    if (!r || !out_bgr) return CL2_E_INVALID;
-    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "the robust picture holds 3*W*H floats");
-    if (out_stats ? n_stats != 2 * (size_t)r->FB : n_stats != 0)
-        return fail(r, CL2_E_INVALID, "the robust statistics hold 2*W*H floats (or are NULL with n_stats 0)");
+namespace {
+// the state cl2_robust_picture and cl2_denoise_robust need of the buckets
+int robust_ready(cl2_renderer* r) {
     if (!r->d_bkt) return fail(r, CL2_E_STATE, "the robust buckets are off (cl2_set_robust_buckets)");
     if (!r->bkt_valid)
         return fail(r, CL2_E_STATE, "the buckets do not cover every sample in the accumulators (they were switched on or resized after "
                                     "samples, or accumulators were written without their buckets): cl2_reset_accumulators or "
                                     "cl2_write_buckets_packed");
+    return CL2_OK;
+}
+
+// cl2_robust_picture's launch on drained streams, shared with cl2_keep_picture: the picture to `d` (device memory, 3*W*H floats),
+// the statistics to d_stats (or nullptr); returns when the kernel has finished
+int run_robust(cl2_renderer* r, float* d, float2* d_stats) {
+    const size_t FB = (size_t)r->FB;
+    hipLaunchKernelGGL(k_robust_picture, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, r->stream, FB, r->bkt_M, (const float*)r->d_bkt,
+                       d, d_stats);
+    int rc = hipGetLastError() == hipSuccess ? CL2_OK : fail(r, CL2_E_HIP, "k_robust_picture launch failed");
+    if (rc == CL2_OK && hipStreamSynchronize(r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "k_robust_picture failed");
+    return rc;
+}
+}  // namespace
+
+int cl2_robust_picture(cl2_renderer* r, float* out_bgr, size_t n_floats, float* out_stats, size_t n_stats) {
+    if (!r || !out_bgr) return CL2_E_INVALID;
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "the robust picture holds 3*W*H floats");
+    if (out_stats ? n_stats != 2 * (size_t)r->FB : n_stats != 0)
+        return fail(r, CL2_E_INVALID, "the robust statistics hold 2*W*H floats (or are NULL with n_stats 0)");
+    TRY(robust_ready(r));
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
     const size_t FB = (size_t)r->FB;
     float* d = nullptr;
     HIP_TRY(r, hipMalloc(&d, (5 * FB + 1) * sizeof(float)));
     float2* d_stats = out_stats ? reinterpret_cast<float2*>(d + 3 * FB + (FB & 1)) : nullptr;   // 8-byte aligned: 3 FB + (FB & 1) is even
-    hipLaunchKernelGGL(k_robust_picture, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, r->stream, FB, r->bkt_M, (const float*)r->d_bkt,
-                       d, d_stats);
-    int rc = hipGetLastError() == hipSuccess ? CL2_OK : fail(r, CL2_E_HIP, "k_robust_picture launch failed");
-    if (rc == CL2_OK && hipStreamSynchronize(r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "k_robust_picture failed");
+    int rc = run_robust(r, d, d_stats);
     if (rc == CL2_OK && hipMemcpy(out_bgr, d, n_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(r, CL2_E_HIP, "robust picture download failed");
     if (rc == CL2_OK && out_stats && hipMemcpy(out_stats, d_stats, n_stats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
@@ -2330,26 +2358,33 @@ int cl2_robust_picture(cl2_renderer* r, float* out_bgr, size_t n_floats, float* 
 }
 
 // The variance-guided filter (denoise_guided.hpp): cl2_denoise's passes with the luma edge-stop driven by the moments.
-int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
-                       size_t n_floats, float* out_var, size_t n_var) {
-    STAGE_PROLOGUE(r);
-    if (!out_bgr) return fail(r, CL2_E_INVALID, "NULL output");
-    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "denoised picture must hold 3*W*H floats");
-    if (out_var ? n_var != (size_t)r->FB : n_var != 0)
-        return fail(r, CL2_E_INVALID, "guide variance must hold W*H floats (or be NULL with n_var 0)");
+namespace {
+// cl2_denoise_guided / cl2_denoise_robust after their output checks, shared with cl2_keep_picture: the remaining checks and every
+// launch.  `robust`: the input pass reads the buckets (cl2_denoise_robust) instead of accumulators and moments.  `want_var`: the
+// guide variance is carried into d_dn_var.  The last launch writes the (H, W, 3) picture to `dst` (device memory; nullptr: d_dn_out).
+int run_guided(cl2_renderer* r, bool robust, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, bool want_var,
+               float* dst) {
     if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
     auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
     if (bad(sigma_luma) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
     if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
     if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
-    TRY(need_moments(r));
+    if (robust)
+        TRY(robust_ready(r));
+    else
+        TRY(need_moments(r));
     const size_t FB = (size_t)r->FB;
     TRY(need_filter_buffers(r));
     if (!r->d_dn_var) TRY(dev_alloc(r, &r->d_dn_var, FB));
+    if (!dst) dst = r->d_dn_out;
     hipStream_t st = r->stream;
-    float* const dvar = out_var ? r->d_dn_var : nullptr;
-    hipLaunchKernelGGL(k_denoise_guided_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc,
-                       (const float*)r->d_mom, r->d_dn[0], iterations == 0 ? r->d_dn_out : (float*)nullptr, dvar);
+    float* const dvar = want_var ? r->d_dn_var : nullptr;
+    if (robust)
+        hipLaunchKernelGGL(k_denoise_robust_input, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, st, FB, r->bkt_M, (const float*)r->d_bkt,
+                           r->d_dn[0], iterations == 0 ? dst : (float*)nullptr, dvar);
+    else
+        hipLaunchKernelGGL(k_denoise_guided_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc,
+                           (const float*)r->d_mom, r->d_dn[0], iterations == 0 ? dst : (float*)nullptr, dvar);
     HIP_TRY(r, hipGetLastError());
     const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
     const float den_a = sigma_albedo * sigma_albedo;
@@ -2357,7 +2392,7 @@ int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float 
         const int step = 1 << i;
         const float4* cin = r->d_dn[i & 1];
         float4* cout = r->d_dn[(i + 1) & 1];
-        float* out3 = i == iterations - 1 ? r->d_dn_out : nullptr;
+        float* out3 = i == iterations - 1 ? dst : nullptr;
         if (step == 1)
             hipLaunchKernelGGL(k_denoise_guided_pass<1>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
         else if (step == 2)
@@ -2366,57 +2401,123 @@ int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float 
             hipLaunchKernelGGL(k_denoise_guided_pass<0>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
         HIP_TRY(r, hipGetLastError());
     }
-    TRY(drain(r));
+    return drain(r);
+}
+
+// the output checks and the downloads of cl2_denoise_guided and cl2_denoise_robust
+int guided_call(cl2_renderer* r, bool robust, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
+                size_t n_floats, float* out_var, size_t n_var) {
+    STAGE_PROLOGUE(r);
+    if (!out_bgr) return fail(r, CL2_E_INVALID, "NULL output");
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "denoised picture must hold 3*W*H floats");
+    if (out_var ? n_var != (size_t)r->FB : n_var != 0)
+        return fail(r, CL2_E_INVALID, "guide variance must hold W*H floats (or be NULL with n_var 0)");
+    TRY(run_guided(r, robust, iterations, sigma_luma, sigma_depth, sigma_albedo, out_var != nullptr, nullptr));
     HIP_TRY(r, hipMemcpy(out_bgr, r->d_dn_out, n_floats * sizeof(float), hipMemcpyDeviceToHost));
     if (out_var) HIP_TRY(r, hipMemcpy(out_var, r->d_dn_var, n_var * sizeof(float), hipMemcpyDeviceToHost));
     return CL2_OK;
+}
+}  // namespace
+
+int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
+                       size_t n_floats, float* out_var, size_t n_var) {
+    return guided_call(r, false, iterations, sigma_luma, sigma_depth, sigma_albedo, out_bgr, n_floats, out_var, n_var);
 }
 
 // The guided filter on the robust picture (denoise_robust.hpp): colour and guide variance from the kept buckets, then
 // cl2_denoise_guided's passes.  Reads the buckets and the features only.
 int cl2_denoise_robust(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
                        size_t n_floats, float* out_var, size_t n_var) {
-    STAGE_PROLOGUE(r);
-    if (!out_bgr) return fail(r, CL2_E_INVALID, "NULL output");
-    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "denoised picture must hold 3*W*H floats");
-    if (out_var ? n_var != (size_t)r->FB : n_var != 0)
-        return fail(r, CL2_E_INVALID, "guide variance must hold W*H floats (or be NULL with n_var 0)");
-    if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
-    auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
-    if (bad(sigma_luma) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
-    if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
-    if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
-    if (!r->d_bkt) return fail(r, CL2_E_STATE, "the robust buckets are off (cl2_set_robust_buckets)");
-    if (!r->bkt_valid)
-        return fail(r, CL2_E_STATE, "the buckets do not cover every sample in the accumulators (they were switched on or resized after "
-                                    "samples, or accumulators were written without their buckets): cl2_reset_accumulators or "
-                                    "cl2_write_buckets_packed");
-    const size_t FB = (size_t)r->FB;
-    TRY(need_filter_buffers(r));
-    if (!r->d_dn_var) TRY(dev_alloc(r, &r->d_dn_var, FB));
-    hipStream_t st = r->stream;
-    float* const dvar = out_var ? r->d_dn_var : nullptr;
-    hipLaunchKernelGGL(k_denoise_robust_input, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, st, FB, r->bkt_M, (const float*)r->d_bkt,
-                       r->d_dn[0], iterations == 0 ? r->d_dn_out : (float*)nullptr, dvar);
-    HIP_TRY(r, hipGetLastError());
-    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
-    const float den_a = sigma_albedo * sigma_albedo;
-    for (int i = 0; i < iterations; i++) {
-        const int step = 1 << i;
-        const float4* cin = r->d_dn[i & 1];
-        float4* cout = r->d_dn[(i + 1) & 1];
-        float* out3 = i == iterations - 1 ? r->d_dn_out : nullptr;
-        if (step == 1)
-            hipLaunchKernelGGL(k_denoise_guided_pass<1>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
-        else if (step == 2)
-            hipLaunchKernelGGL(k_denoise_guided_pass<2>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
-        else
-            hipLaunchKernelGGL(k_denoise_guided_pass<0>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
-        HIP_TRY(r, hipGetLastError());
-    }
+    return guided_call(r, true, iterations, sigma_luma, sigma_depth, sigma_albedo, out_bgr, n_floats, out_var, n_var);
+}
+
+// ---------------------------------------------------------------- kept picture and its tone map (csrc/tonemap_picture.hpp)
+namespace {
+int need_picture(cl2_renderer* r) {
+    if (!r->pic_kind) return fail(r, CL2_E_STATE, "no kept picture (cl2_keep_picture or cl2_write_picture first)");
+    return CL2_OK;
+}
+}  // namespace
+
+int cl2_keep_picture(cl2_renderer* r, int kind, int iterations, float sigma, float sigma_depth, float sigma_albedo) {
+    if (!r) return CL2_E_INVALID;
+    if (kind < 0 || kind > 4) return fail(r, CL2_E_INVALID, "kept picture: 0 none, 1 denoised, 2 guided, 3 robust, 4 robust-guided");
+    HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
-    HIP_TRY(r, hipMemcpy(out_bgr, r->d_dn_out, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_var) HIP_TRY(r, hipMemcpy(out_var, r->d_dn_var, n_var * sizeof(float), hipMemcpyDeviceToHost));
+    if (kind == 0) {
+        dev_free(r, r->d_pic);
+        r->pic_kind = 0;
+        return CL2_OK;
+    }
+    if (kind == 3)
+        TRY(robust_ready(r));
+    else
+        STAGE_PROLOGUE(r);
+    const bool fresh = !r->d_pic;
+    if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
+    int rc;
+    if (kind == 1) rc = run_denoise(r, iterations, sigma, sigma_depth, sigma_albedo, r->d_pic);
+    else if (kind == 3) rc = run_robust(r, r->d_pic, nullptr);
+    else rc = run_guided(r, kind == 4, iterations, sigma, sigma_depth, sigma_albedo, false, r->d_pic);
+    if (rc == CL2_OK) r->pic_kind = kind;
+    else if (rc == CL2_E_HIP) r->pic_kind = 0;                    // launches may have written part of it
+    // every other refusal comes before the first launch: the previous picture stands; a buffer made for this call goes again
+    if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);
+    return rc;
+}
+
+int cl2_kept_picture(const cl2_renderer* r) { return r ? r->pic_kind : 0; }
+
+int cl2_write_picture(cl2_renderer* r, const float* bgr, size_t n_floats) {
+    if (!r || !bgr) return CL2_E_INVALID;
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "the kept picture holds 3*W*H floats");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    if (!r->d_pic) TRY(dev_alloc(r, &r->d_pic, n_floats));
+    r->pic_kind = 0;
+    HIP_TRY(r, hipMemcpy(r->d_pic, bgr, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    r->pic_kind = 5;
+    return CL2_OK;
+}
+
+int cl2_read_picture(cl2_renderer* r, float* out_bgr, size_t n_floats) {
+    if (!r || !out_bgr) return CL2_E_INVALID;
+    if (n_floats != 3 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "the kept picture holds 3*W*H floats");
+    TRY(need_picture(r));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(out_bgr, r->d_pic, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+
+int cl2_picture_log_sum(cl2_renderer* r, double* sum_out) {
+    if (!r || !sum_out) return CL2_E_INVALID;
+    TRY(need_picture(r));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    TRY(tone_buffers(r));
+    const int grid = std::min(grid_for(r->FB), TONE_BLOCKS);
+    hipLaunchKernelGGL(k_picture_logsum, dim3(grid), dim3(256), 0, r->stream, (const float*)r->d_pic, r->FB, r->d_tone_partial);
+    hipLaunchKernelGGL(k_tone_logsum_final, dim3(1), dim3(256), 0, r->stream, r->d_tone_partial, grid, r->d_tone_partial + TONE_BLOCKS);
+    HIP_TRY(r, hipGetLastError());
+    HIP_TRY(r, hipMemcpyAsync(sum_out, r->d_tone_partial + TONE_BLOCKS, sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    return CL2_OK;
+}
+
+int cl2_picture_tone_map(cl2_renderer* r, double exposure, double white_point, double log_average, uint8_t* out_bgr, size_t n_bytes) {
+    if (!r || !out_bgr) return CL2_E_INVALID;
+    if (n_bytes != (size_t)3 * r->FB) return fail(r, CL2_E_INVALID, "the tone-mapped picture holds 3*W*H bytes");
+    TRY(need_picture(r));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    TRY(tone_buffers(r));
+    const size_t quads = (n_bytes + 3) / 4;                       // four values per thread (k_picture_apply)
+    hipLaunchKernelGGL(k_picture_apply, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, r->stream, (const float*)r->d_pic, n_bytes,
+                       (float)exposure, white_point * white_point, log_average, r->d_tone_out);
+    HIP_TRY(r, hipGetLastError());
+    HIP_TRY(r, hipMemcpyAsync(out_bgr, r->d_tone_out, n_bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
     return CL2_OK;
 }
 

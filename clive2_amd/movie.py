@@ -44,6 +44,10 @@ def main(argv=None):
     ap.add_argument("--out-root", type=str, default="../output")
     ap.add_argument("--host-tonemap", action="store_true",
                     help="tone-map every frame on the host with numpy (the reference's path, Renderer.image) instead of on the device")
+    ap.add_argument("--device-tonemap", action="store_true",
+                    help="with --denoise, --variance-guided, --robust or --robust-denoise: keep the derived picture on the device and "
+                         "tone-map it there (Renderer.tone_mapped, DESIGN.md 6.9) instead of copying it out as float32 and mapping it with "
+                         "numpy; the plain picture is tone-mapped on the device already.  Not with --host-tonemap")
     ap.add_argument("--denoise", action="store_true",
                     help="after each frame's samples, render its first-hit features and save the denoised picture (Renderer.denoised_image)")
     ap.add_argument("--feature-samples", type=int, default=4, help="camera rays per pixel of the feature pass of --denoise")
@@ -62,12 +66,12 @@ def main(argv=None):
                     help=f"share of the density that stays uniform under --adaptive, in (0, 1] (default {UNIFORM_SHARE})")
     ap.add_argument("--robust", type=int, nargs="?", const=8, default=0, metavar="M",
                     help="save the firefly-robust picture: a Gini-trimmed median of means over M buckets per pixel, 3..16 "
-                         "(Renderer.robust_image, DESIGN.md 6.7; default 8; tone-mapped on the host).  Goes with --target-error and "
+                         "(Renderer.robust_image, DESIGN.md 6.7; default 8; tone-mapped on the host unless --device-tonemap).  Goes with --target-error and "
                          "--adaptive (the error metric stays on the plain estimates), not with --denoise")
     ap.add_argument("--robust-denoise", type=int, nargs="?", const=8, default=0, metavar="M",
                     help="save the robust picture after the variance-guided filter, guided by the variance of the buckets the trim "
                          "kept (Renderer.robust_guided_image, DESIGN.md 6.8): M buckets per pixel, 3..16, default 8; the feature pass "
-                         "takes --feature-samples; tone-mapped on the host.  Goes with --target-error and --adaptive (the error "
+                         "takes --feature-samples; tone-mapped on the host unless --device-tonemap.  Goes with --target-error and --adaptive (the error "
                          "metric stays on the plain estimates), not with --robust, --denoise or --variance-guided")
     args = ap.parse_args(argv)
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
@@ -90,6 +94,8 @@ def main(argv=None):
         ap.error("--robust-denoise is a picture of its own: it does not go with --robust, --denoise or --variance-guided")
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
+    if args.device_tonemap and args.host_tonemap:
+        ap.error("--device-tonemap does not go with --host-tonemap")
 
     rank, local_rank, world = rank_info()
     out_dir = os.path.join(args.out_root, args.movie_name)
@@ -120,14 +126,18 @@ def main(argv=None):
         else:
             renderer.run_samples(args.samples)
         # a frame leaves the device tone-mapped (6 MB at 1080p; Renderer.image reads 66 MB of accumulators and maps them with numpy)
+        dev = args.device_tonemap
         if args.robust:
-            image = renderer.robust_image
+            image = renderer.tone_mapped("robust") if dev else renderer.robust_image
         elif args.robust_denoise:
             renderer.render_features(args.feature_samples)
-            image = renderer.robust_guided_image
+            image = renderer.tone_mapped("robust_guided") if dev else renderer.robust_guided_image
         elif args.denoise:
             renderer.render_features(args.feature_samples)
-            image = renderer.guided_image if args.variance_guided else renderer.denoised_image
+            if dev:
+                image = renderer.tone_mapped("guided" if args.variance_guided else "denoised")
+            else:
+                image = renderer.guided_image if args.variance_guided else renderer.denoised_image
         else:
             image = renderer.image if args.host_tonemap else renderer.tone_mapped("image")
         save_frame(os.path.join(out_dir, f"frame_{f:04d}.png"), image)

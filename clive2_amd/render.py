@@ -34,7 +34,9 @@ def main(argv=None):
     ap.add_argument("--out", type=str, default="render.png")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--device-tonemap", action="store_true",
-                    help="tone-map on the device (Renderer.tone_mapped) instead of on the host with numpy (Renderer.image, the reference's path)")
+                    help="tone-map on the device (Renderer.tone_mapped) instead of on the host with numpy (Renderer.image, the reference's "
+                         "path); with --denoise, --variance-guided, --robust and --robust-denoise the derived picture stays on the device "
+                         "and is tone-mapped there too (DESIGN.md 6.9)")
     ap.add_argument("--sample-streams", type=lambda v: v if v == "auto" else int(v), default=1,
                     help="K independent samples of the frame per pass (Renderer(streams=K): one seed buffer each, as K renderers "
                          "would hold; pays on mesh scenes, where it makes every launch K times larger); the samples are rounded up "
@@ -63,12 +65,12 @@ def main(argv=None):
                     help="save the per-pixel standard error (Renderer.standard_error: (H, W, 4) float32 b, g, r, luma) as .npy")
     ap.add_argument("--robust", type=int, nargs="?", const=8, default=0, metavar="M",
                     help="save the firefly-robust picture: a Gini-trimmed median of means over M buckets per pixel, 3..16 "
-                         "(Renderer.robust_image, DESIGN.md 6.7; default 8; tone-mapped on the host).  Goes with --target-error and "
+                         "(Renderer.robust_image, DESIGN.md 6.7; default 8; tone-mapped on the host unless --device-tonemap).  Goes with --target-error and "
                          "--adaptive (the error metric stays on the plain estimates), not with --denoise")
     ap.add_argument("--robust-denoise", type=int, nargs="?", const=8, default=0, metavar="M",
                     help="save the robust picture after the variance-guided filter, guided by the variance of the buckets the trim "
                          "kept (Renderer.robust_guided_image, DESIGN.md 6.8): M buckets per pixel, 3..16, default 8; the feature pass "
-                         "takes --feature-samples; tone-mapped on the host.  Goes with --target-error and --adaptive (the error "
+                         "takes --feature-samples; tone-mapped on the host unless --device-tonemap.  Goes with --target-error and --adaptive (the error "
                          "metric stays on the plain estimates), not with --robust, --denoise or --variance-guided")
     args = ap.parse_args(argv)
     # refused before any renderer is made
@@ -157,20 +159,24 @@ def main(argv=None):
     # Tone-mapped uint8, BGR.  The film sits BEHIND the pinhole, so the picture on it is already upright
     # when read row 0 first (row 0 looks up at the ceiling light): the reference hands `renderer.image`
     # to cv2 unflipped (render.py:35-37).  Only the channel order changes for a PNG (BGR -> RGB).
+    dev = args.device_tonemap
     if args.robust:
-        image = renderer.robust_image
+        image = renderer.tone_mapped("robust") if dev else renderer.robust_image
     elif args.robust_denoise:
         t1 = time.time()
         renderer.render_features(args.feature_samples)
-        image = renderer.robust_guided_image
+        image = renderer.tone_mapped("robust_guided") if dev else renderer.robust_guided_image
         print(f"[rank {rank}] features ({args.feature_samples} rays per pixel) and denoising took {time.time() - t1:.2f} seconds")
     elif args.denoise:
         t1 = time.time()
         renderer.render_features(args.feature_samples)
-        image = renderer.guided_image if args.variance_guided else renderer.denoised_image
+        if dev:
+            image = renderer.tone_mapped("guided" if args.variance_guided else "denoised")
+        else:
+            image = renderer.guided_image if args.variance_guided else renderer.denoised_image
         print(f"[rank {rank}] features ({args.feature_samples} rays per pixel) and denoising took {time.time() - t1:.2f} seconds")
     else:
-        image = renderer.tone_mapped("image") if args.device_tonemap else renderer.image
+        image = renderer.tone_mapped("image") if dev else renderer.image
     renderer.close()
     try:
         from PIL import Image

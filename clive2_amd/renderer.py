@@ -247,7 +247,15 @@ class Renderer:
         then differ from `.image` by one count where 255*x/(x+w) lies within ~1e-13 (relative) of an integer.  Among ordinary
         pixels that is rare; a saturated pixel (x > 2^53, so x + w == x) always sits there: fl(255*x)/x is 255 or the double
         below it by the last bits of x, so many such bytes trade 254 for 255 at once (tests/tone_reference.py: fragile).
-        `log_average`: use this Lw instead of the picture's own (no log-sum launch)."""
+        `log_average`: use this Lw instead of the picture's own (no log-sum launch).
+
+        `which` may also be "denoised", "guided", "robust" or "robust_guided": keep_picture(which) with the defaults, then
+        tone_mapped_picture() -- the device counterpart of denoised_image, guided_image, robust_image and robust_guided_image.
+        This REPLACES the kept picture."""
+        if which in self._KEPT_KINDS:
+            self._numpy2("tone_mapped()")
+            self.keep_picture(which)
+            return self.tone_mapped_picture(exposure, white_point, log_average)
         w = self._PICTURES[which]
         # the device arithmetic restates what numpy >= 2 (NEP 50 promotion) makes of camera.py:73-82: the float32 picture times
         # the exposure stays float32 and is widened by the division by the float64 Lw.  numpy 1.x keeps `result` in float32
@@ -261,6 +269,81 @@ class Renderer:
         out = np.empty((self.pixel_height, self.pixel_width, 3), np.uint8)
         self._check(self._L.cl2_tone_map(self._h, w, float(exposure), float(white_point), float(log_avg), ptr(out),
                                          C.c_size_t(out.size)), "cl2_tone_map")
+        return out
+
+    # ---- a kept picture and its tone map on the device (cl2_keep_picture ... cl2_picture_tone_map, csrc/tonemap_picture.hpp) ----
+    _KEPT_KINDS = {"denoised": 1, "guided": 2, "robust": 3, "robust_guided": 4}
+    _KEPT_NAMES = {0: None, 1: "denoised", 2: "guided", 3: "robust", 4: "robust_guided", 5: "loaded"}
+
+    @staticmethod
+    def _numpy2(what):
+        if int(np.__version__.split(".")[0]) < 2:
+            raise RendererError(f"{what} reproduces the reference's tone map under numpy >= 2 (NEP 50) only; use the *_image properties")
+
+    def keep_picture(self, kind, **params):
+        """Compute one of the derived pictures and KEEP it in device memory instead of copying it to the host: `kind` is
+        "denoised" (denoised_radiance), "guided" (guided_radiance), "robust" (robust_radiance), "robust_guided"
+        (robust_guided_radiance) or None (drop the kept picture and free its 12*W*H bytes).  `params` are the filter arguments of
+        the corresponding method (iterations, sigma_color or sigma_luma, sigma_depth, sigma_albedo); unset ones take
+        DENOISE_DEFAULTS, GUIDED_DEFAULTS or ROBUST_GUIDED_DEFAULTS; "robust" takes none.  Same launches, same checks and same
+        errors as that method.  The kept picture is a snapshot: later samples, resets and scene uploads do not change it; a
+        refused call leaves the previous one in place."""
+        if kind is None:
+            if params:
+                raise TypeError("keep_picture(None) takes no filter arguments")
+            self._check(self._L.cl2_keep_picture(self._h, 0, 0, 0.0, 0.0, 0.0), "cl2_keep_picture")
+            return
+        if kind not in self._KEPT_KINDS:
+            raise ValueError(f"kept picture: one of {sorted(self._KEPT_KINDS)} or None, not {kind!r}")
+        d = {"denoised": self.DENOISE_DEFAULTS, "guided": self.GUIDED_DEFAULTS, "robust": {},
+             "robust_guided": self.ROBUST_GUIDED_DEFAULTS}[kind]
+        unknown = sorted(set(params) - set(d))
+        if unknown:
+            raise TypeError(f"keep_picture({kind!r}) takes {sorted(d)}, not {unknown}")
+        a = {k: (v if params.get(k) is None else params[k]) for k, v in d.items()}
+        sigma = a.get("sigma_color", a.get("sigma_luma", 0.0))
+        self._check(self._L.cl2_keep_picture(self._h, self._KEPT_KINDS[kind], int(a.get("iterations", 0)), float(sigma),
+                                             float(a.get("sigma_depth", 0.0)), float(a.get("sigma_albedo", 0.0))), "cl2_keep_picture")
+
+    @property
+    def kept_kind(self):
+        """what the handle keeps: None, "denoised", "guided", "robust", "robust_guided" or "loaded" (load_picture)"""
+        return self._KEPT_NAMES[int(self._L.cl2_kept_picture(self._h))]
+
+    def kept_picture(self):
+        """The kept picture: float32 (H,W,3), BGR -- for kinds made by keep_picture, byte for byte what the corresponding
+        *_radiance method returns."""
+        out = np.empty((self.pixel_height, self.pixel_width, 3), np.float32)
+        self._check(self._L.cl2_read_picture(self._h, ptr(out), C.c_size_t(out.size)), "cl2_read_picture")
+        return out
+
+    def load_picture(self, a):
+        """Make `a` (3*W*H float32 values, (H,W,3) BGR) the kept picture (kind "loaded"): any float picture can take the device
+        tone map, and tests inject states."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        self._check(self._L.cl2_write_picture(self._h, ptr(a), C.c_size_t(a.size)), "cl2_write_picture")
+
+    def picture_log_sum(self):
+        """Sum over the pixels of log(0.1 + luma) of the kept picture, in float64, on the device (cl2_picture_log_sum).  There is
+        no scrub: NaN where a pixel is NaN or its luma is below -0.1, as numpy's sum on the host."""
+        s = C.c_double(0.0)
+        self._check(self._L.cl2_picture_log_sum(self._h, C.byref(s)), "cl2_picture_log_sum")
+        return float(s.value)
+
+    def tone_mapped_picture(self, exposure=4.0, white_point=1.0, log_average=None):
+        """`tone_map` (camera.py:73-82) of the kept picture ON THE DEVICE: uint8 (H,W,3), BGR; 3*W*H bytes cross PCIe where the
+        *_image properties copy 12*W*H and map them with numpy.  Given the same Lw the bytes are the host's tone_map(kept_picture()),
+        every one; the float64 log sum is added in another order, so Lw can differ in its last bits and a byte can then differ by
+        one count where 255*x/(x+w) lies within ~1e-13 (relative) of an integer (tone_mapped()'s docstring;
+        tests/picture_tone_reference.py: fragile).  `log_average`: use this Lw instead of the picture's own."""
+        self._numpy2("tone_mapped_picture()")
+        if log_average is None:
+            log_avg = np.exp(np.float64(self.picture_log_sum()) / (self.pixel_height * self.pixel_width))   # Lw, with numpy's exp
+        else:
+            log_avg = log_average
+        out = np.empty((self.pixel_height, self.pixel_width, 3), np.uint8)
+        self._check(self._L.cl2_picture_tone_map(self._h, float(exposure), float(white_point), float(log_avg), ptr(out),
+                                                 C.c_size_t(out.size)), "cl2_picture_tone_map")
         return out
 
     @property

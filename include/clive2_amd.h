@@ -556,6 +556,40 @@ int cl2_robust_picture(cl2_renderer* r, float* out_bgr, size_t n_floats, float* 
 int cl2_denoise_robust(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
                        size_t n_floats, float* out_var, size_t n_var);
 
+/* ---- a kept picture and its tone map on the device (csrc/tonemap_picture.hpp) ----
+ * The handle can keep ONE picture in device memory: (H, W, 3) float32 b, g, r, 12*W*H bytes, allocated on first use.  Its kind:
+ *     0 none   1 denoised (cl2_denoise)   2 guided (cl2_denoise_guided)   3 robust (cl2_robust_picture)
+ *     4 robust-guided (cl2_denoise_robust)   5 loaded (cl2_write_picture)
+ * It is a snapshot: it holds until it is replaced, dropped (kind 0) or the handle is destroyed; later samples, resets and scene
+ * uploads do not change it.
+ *
+ * cl2_keep_picture, kinds 1..4: exactly the launches of the call named above, with the same argument checks, the same CL2_E_STATE
+ * conditions and the same messages; the last launch writes into the kept picture instead of the call's own output buffer, and
+ * nothing is copied to the host.  `sigma` is sigma_color for kind 1 and sigma_luma for kinds 2 and 4; kind 3 ignores the four filter
+ * arguments.  Kind 0 drops the picture and frees its buffer; any other kind is CL2_E_INVALID.  A refused call leaves the previous
+ * kept picture as it was; a HIP failure part way through leaves kind 0.  The call touches what the corresponding call above
+ * touches (the filters' working buffers) and the kept picture, nothing else.
+ * cl2_kept_picture: the kind; 0 for none or a NULL handle (a plain read of the handle: no device work).
+ * cl2_write_picture / cl2_read_picture: the picture as host floats, n_floats = 3*W*H (else CL2_E_INVALID); writing makes kind 5.
+ * cl2_picture_log_sum / cl2_picture_tone_map: cl2_tone_log_sum and cl2_tone_map for the kept picture.  Per pixel, f the picture's
+ * float32 value, c the channel:
+ *     base_c = (double)f_c    luma = (base_b * 0.0722 + base_g * 0.7152) + base_r * 0.2126    term = log(0.1 + luma)
+ *     pre_c = (double)(f_c * (float)exposure)  (a float32 product)    result = pre_c / Lw    v = 255 * result / (result + white_point^2)
+ *     byte = cl2_tone_map's cast of v
+ * This is picture 0's arithmetic WITHOUT the scrub, as the host path tone_map(picture) has none: a NaN pixel makes the log sum NaN
+ * and the picture all zero bytes, exactly as on the host.  The sum is added in cl2_tone_log_sum's order (same workgroups, same tree).
+ * n_bytes = 3*W*H.  The two share the partial-sum and byte buffers of cl2_tone_log_sum / cl2_tone_map.
+ * cl2_read_picture, cl2_picture_log_sum and cl2_picture_tone_map return CL2_E_STATE without a kept picture; NULL pointers and wrong
+ * sizes are CL2_E_INVALID.  All calls but cl2_kept_picture drain the handle's streams first.  None of them touches seeds,
+ * accumulators, moments, buckets, features or counters. */
+int cl2_keep_picture(cl2_renderer* r, int kind, int iterations, float sigma, float sigma_depth, float sigma_albedo);
+int cl2_kept_picture(const cl2_renderer* r);
+int cl2_write_picture(cl2_renderer* r, const float* bgr, size_t n_floats);
+int cl2_read_picture(cl2_renderer* r, float* out_bgr, size_t n_floats);
+int cl2_picture_log_sum(cl2_renderer* r, double* sum_out);
+int cl2_picture_tone_map(cl2_renderer* r, double exposure, double white_point, double log_average /* Lw */, uint8_t* out_bgr,
+                         size_t n_bytes);
+
 #ifdef __cplusplus
 }
 #endif
