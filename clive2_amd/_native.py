@@ -56,7 +56,7 @@ class Organisation(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("tree_in_lds", "persistent_subpaths", "persistent_connections", "two_tris_per_step",
                                          "n_records", "n_lds_records", "n_top_renumbered", "lds_triangles",
                                          "levels_per_launch", "paths_share", "pipeline_stages", "wide_connections", "wide_nodes", "pruned_records")] + \
-               [("tree_bytes", C.c_int64), ("sample_streams", C.c_int32), ("reserved", C.c_int32)]
+               [("tree_bytes", C.c_int64), ("sample_streams", C.c_int32), ("staged_bytes", C.c_int32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

@@ -43,6 +43,7 @@ struct BvhView {
                                 // same hits for rays with finite 1/d, fewer box tests
     int fast_flat;              // 1: the pruned table is a plain list of leaves (every record a leaf, skip = index + 1): every lane
                                 // visits the same records in the same order, so the walk's control flow is wave-uniform
+                                // (closest_hit_flat); 2: the same, walked by closest_hit_flat_clamped (debug bit 26)
 };
 
 // The staged part of the tree lives in DYNAMIC shared memory sized by the scene (bvh_lds_bytes on the
@@ -55,15 +56,23 @@ struct BvhLds {
 };
 
 // Cooperative copy of the staged part of the tree; every thread of the block must call it.
+// LDS_TRI_PADS pad records stand behind the staged triangles: copies of the last record that are fetched and never tested.  The
+// flat walk (closest_hit_flat) fetches the record behind the one it tests without a clamp; behind a leaf's last triangle that is
+// the next leaf's first record, and behind the array's last triangle a pad (scene_layout.hpp; the host counts them).  The
+// walk as written reaches one record behind the array at most (it fetches i + 2 only while i + 1 is still inside the leaf), so
+// one pad would do; the second is room for a loop that runs two records ahead.  Needs n_tris >= 1 (cl2_upload_scene refuses a
+// scene without triangles) and a block of at least 3 * LDS_TRI_PADS threads (every caller launches BLOCK = 256).
 __device__ __forceinline__ void stage_bvh(BvhLds& s, const BvhView& b) {
     extern __shared__ float4 cl2_tree_lds[];
     float4* nodes = cl2_tree_lds;
     float4* tris = cl2_tree_lds + 2 * b.n_lds_nodes;
     const int nt = blockDim.x, t = threadIdx.x;
     for (int i = t; i < 2 * b.n_lds_nodes; i += nt) nodes[i] = b.nodes[i];
-    float4* fast = tris + (b.lds_tris ? 3 * b.n_tris : 0);
-    if (b.lds_tris)
+    float4* fast = tris + (b.lds_tris ? 3 * (b.n_tris + LDS_TRI_PADS) : 0);
+    if (b.lds_tris) {
         for (int i = t; i < 3 * b.n_tris; i += nt) tris[i] = b.tris[i];
+        if (t < 3 * LDS_TRI_PADS) tris[3 * b.n_tris + t] = b.tris[3 * (b.n_tris - 1) + t % 3];
+    }
     for (int i = t; i < 2 * b.n_fast_nodes; i += nt) fast[i] = b.fast_nodes[i];
     s.nodes = nodes; s.tris = tris; s.fast_nodes = fast;
     __syncthreads();
@@ -136,10 +145,12 @@ __device__ __forceinline__ Hit closest_hit_impl(const BvhLds& s, const BvhView& 
 }
 
 // ray_triangle_intersect, trace.metal:117-142, against a fetched record {v0, e1, e2}; keeps the hit on strict t < best.t
+// (W2: the reciprocal with the two-instruction window test, vecmath.hpp -- the same value)
+template <bool W2>
 __device__ __forceinline__ void tri_test(V3 o, V3 d, float4 a0, float4 a1, float4 a2, int index, Hit& best) {
     const V3 e1 = v3(a1), e2 = v3(a2);
     const V3 h = cross(d, e2);
-    const float f = rcp_exact(dot(e1, h));
+    const float f = W2 ? rcp_exact_w(dot(e1, h)) : rcp_exact(dot(e1, h));
     const V3 sv = o - v3(a0);
     const float u = f * dot(sv, h);
     if (!(u < 0 || u > 1)) {
@@ -227,6 +238,59 @@ __device__ __forceinline__ bool tri_test_branchless_tie(V3 o, V3 d, const float4
 // Per lane the sequence of box tests, triangle tests and comparisons is exactly that of closest_hit_impl<.., true, true>
 // on the same table.  Only for waves whose rays all have finite 1/d (v_min / v_max slab test), never while counting.
 __device__ __forceinline__ Hit closest_hit_flat(const BvhLds& s, const BvhView& b, V3 o, V3 d, V3 inv) {
+    typedef float __attribute__((ext_vector_type(4))) Raw4;
+    typedef const __attribute__((address_space(3))) Raw4* LdsRec;
+    auto rec = [](LdsRec p, int k) { const Raw4 v = p[k]; return make_float4(v.x, v.y, v.z, v.w); };
+    // keep4() makes the unused fourth word of a record live, so that each float4 comes by one ds_read_b128 (4 LDS cycles) and
+    // not by the ds_read_b96 the compiler would narrow it to (8 LDS cycles, MI355X_MICROARCH.md "LDS").
+    auto keep4 = [](float4& v) { asm volatile("" : "+v"(v.w)); };
+    Hit best{-1, __builtin_inff(), 0.0f, 0.0f};
+    const int n = b.n_fast_nodes;
+    const unsigned tri_base = (unsigned)(size_t)s.tris;    // LDS byte address: the low half of the generic pointer
+    for (int node = 0; node < n; node++) {
+        // the leaf record in two 16-byte reads; `info` is the fourth word of the second, so no third read follows the box test
+        float4 lo = s.fast_nodes[2 * node], hi = s.fast_nodes[2 * node + 1];
+        const float t0x = (lo.x - o.x) * inv.x, t0y = (lo.y - o.y) * inv.y, t0z = (lo.z - o.z) * inv.z;
+        const float t1x = (hi.x - o.x) * inv.x, t1y = (hi.y - o.y) * inv.y, t1z = (hi.z - o.z) * inv.z;
+        const float tmin = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t0x, t1x), __builtin_fminf(t0y, t1y)),
+                                           __builtin_fmaxf(__builtin_fminf(t0z, t1z), 0.0f));
+        const float tmax = __builtin_fminf(__builtin_fmaxf(t0x, t1x), __builtin_fminf(__builtin_fmaxf(t0y, t1y), __builtin_fmaxf(t0z, t1z)));
+        const bool in = tmin <= tmax && tmin < best.t;
+        keep4(lo); keep4(hi);
+        const int info = __builtin_amdgcn_readfirstlane(__float_as_int(hi.w));      // the same word in every lane
+        if (!__any(in)) continue;
+        const int left = info >> 4, right = left + (info & 15) + 1;
+        // Two register sets in turn: the record of triangle i + 1 is on its way while triangle i is tested.  The fetch is
+        // unconditional and unclamped (behind the array's last triangle stand the pad records of stage_bvh): a branch around it
+        // makes the compiler wait for ALL outstanding LDS reads at the join instead of counting them, and a clamp costs eight
+        // scalar instructions per triangle.  The address of record i lives in ONE vector register (the empty asm takes it out of
+        // the scalar unit's hands): the six reads of a trip are offset: immediates of it, one v_add_u32 per trip advances it, and
+        // the scalar side is left with the triangle index alone.
+        unsigned at = tri_base + 48u * (unsigned)left;
+        asm volatile("" : "+v"(at));
+        LdsRec p = (LdsRec)(size_t)at;
+        float4 a0 = rec(p, 0), a1 = rec(p, 1), a2 = rec(p, 2), c0, c1, c2;
+        for (int i = left;;) {
+            c0 = rec(p, 3); c1 = rec(p, 4); c2 = rec(p, 5);
+            if (in) tri_test<true>(o, d, a0, a1, a2, i, best);
+            keep4(a0); keep4(a1); keep4(a2);        // here, where the record has been consumed: the asm waits for its operand
+            if (++i == right) break;
+            a0 = rec(p, 6); a1 = rec(p, 7); a2 = rec(p, 8);
+            if (in) tri_test<true>(o, d, c0, c1, c2, i, best);
+            keep4(c0); keep4(c1); keep4(c2);
+            if (++i == right) break;
+            p += 6;
+        }
+    }
+    return best;
+}
+
+// The walk as it was before the pad records: next-record index clamped on the scalar unit, leaf record read as the compiler
+// narrows it, the reciprocal's window test in three instructions.  Same tests in the same order; kept behind debug bit 26
+// (b.fast_flat == 2) for A/B runs and parity tests.  The choice is made at run time, so every kernel that walks the flat table
+// (k_connect_walk_lds, k_trace_subpath, k_traverse_conn, k_traverse_paths) carries both loops: about 1.4 KB more code each
+// (k_connect_walk_lds 29.3 -> 30.7 KB of a 64 KB instruction cache shared by two CUs); the timings of profiles/r17 include it.
+__device__ __forceinline__ Hit closest_hit_flat_clamped(const BvhLds& s, const BvhView& b, V3 o, V3 d, V3 inv) {
     Hit best{-1, __builtin_inff(), 0.0f, 0.0f};
     const int n = b.n_fast_nodes;
     for (int node = 0; node < n; node++) {
@@ -254,11 +318,11 @@ __device__ __forceinline__ Hit closest_hit_flat(const BvhLds& s, const BvhView& 
         fetch(left, a0, a1, a2);
         for (int i = left;;) {
             fetch(i < last ? i + 1 : last, c0, c1, c2);
-            if (in) tri_test(o, d, a0, a1, a2, i, best);
+            if (in) tri_test<false>(o, d, a0, a1, a2, i, best);
             keep4(a0); keep4(a1); keep4(a2);        // here, where the record has been consumed: the asm waits for its operand
             if (++i > last) break;
             fetch(i < last ? i + 1 : last, a0, a1, a2);
-            if (in) tri_test(o, d, c0, c1, c2, i, best);
+            if (in) tri_test<false>(o, d, c0, c1, c2, i, best);
             keep4(c0); keep4(c1); keep4(c2);
             if (++i > last) break;
         }
@@ -286,7 +350,8 @@ __device__ __forceinline__ Hit closest_hit(const BvhLds& s, const BvhView& b, V3
     const bool fast = __all(finite3(inv));
     if (all_lds) {
         // the pruned table: not while counting (the tallies are those of the full walk)
-        if (fast && !COUNT && b.n_fast_nodes && b.fast_flat) return closest_hit_flat(s, b, o, d, inv);
+        if (fast && !COUNT && b.n_fast_nodes && b.fast_flat)
+            return b.fast_flat == 2 ? closest_hit_flat_clamped(s, b, o, d, inv) : closest_hit_flat(s, b, o, d, inv);
         if (fast && !COUNT && b.n_fast_nodes) return closest_hit_impl<COUNT, true, true>(s, b, o, d, inv, n_box, n_tri, s.fast_nodes, b.n_fast_nodes);
         if (fast) return closest_hit_impl<COUNT, true, true>(s, b, o, d, inv, n_box, n_tri, s.nodes, b.n_nodes);
         return closest_hit_impl<COUNT, true, false>(s, b, o, d, inv, n_box, n_tri, s.nodes, b.n_nodes);

@@ -884,8 +884,8 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_subpaths_persistent(
                     tri_test_branchless(o, d, a0, a1, a2, i0, best);
                     if (TWO_TRIS) tri_test_branchless(o, d, c0, c1, c2, i1, best);
                 } else {
-                    tri_test(o, d, a0, a1, a2, i0, best);
-                    if (TWO_TRIS && two) tri_test(o, d, c0, c1, c2, i1, best);
+                    tri_test<false>(o, d, a0, a1, a2, i0, best);
+                    if (TWO_TRIS && two) tri_test<false>(o, d, c0, c1, c2, i1, best);
                 }
             }
             if (tri_i >= tri_end && ((WIDE && wlane) ? (cur < 0 && sp == 0) : node >= n_nodes)) state = LANE_PEND;

@@ -307,9 +307,9 @@ int launch_generate_both(cl2_renderer* r, hipStream_t st, const PathBufs* set, c
 // In serial order fused wins on mid-size trees (5k-triangle sphere: 5.7 vs 8.7 ms per sample), but
 // the sample pipeline with stage shares hides the tails of the persistent form and then the two are
 // equal there (6.05 vs 6.00 Grays/s) and persistent wins from 82k triangles on (4.7 vs 3.9).
-// dynamic shared memory of a launch that stages the tree (stage_bvh)
+// dynamic shared memory of a launch that stages the tree (stage_bvh), the pad records behind the triangles included
 inline size_t bvh_lds_bytes(const cl2_renderer* r) {
-    return ((size_t)2 * r->bvh.n_lds_nodes + (r->bvh.lds_tris ? (size_t)3 * r->bvh.n_tris : 0) + (size_t)2 * r->bvh.n_fast_nodes) * sizeof(float4);
+    return ((size_t)2 * r->bvh.n_lds_nodes + (r->bvh.lds_tris ? (size_t)3 * (r->bvh.n_tris + LDS_TRI_PADS) : 0) + (size_t)2 * r->bvh.n_fast_nodes) * sizeof(float4);
 }
 // counting mode 1: the node / triangle tallies of the REFERENCE's walk (binary stackless walk; the wide walk steps aside);
 // mode 2 tallies what the 4-wide walk itself fetches and changes no launch but the whole-subpath one (see whole_subpaths)
@@ -325,6 +325,11 @@ inline bool split_conn(const cl2_renderer* r) {
 }
 // Connection set-up and walk fused into one launch (k_connect_walk_lds): trees wholly staged in LDS whose pruned table is a
 // flat list of leaves (closest_hit_flat), one ray per lane, not while counting.  Debug bit 25 keeps the two launches (A/B).
+// Debug bit 26 walks the flat table with the clamped loop (closest_hit_flat_clamped) in every launch that walks it.
+inline int flat_walk(const cl2_renderer* r) {
+    if (!r->fast_flat || ((r->debug_flags >> 11) & 1)) return 0;
+    return ((r->debug_flags >> 26) & 1) ? 2 : 1;
+}
 inline bool fused_conn(const cl2_renderer* r) {
     return tree_in_lds(r) && !split_conn(r) && !count_ref(r) && r->bvh.n_fast_nodes > 0 && r->bvh.fast_flat &&
            !((r->debug_flags >> 25) & 1);
@@ -1020,7 +1025,7 @@ int cl2_upload_scene(cl2_renderer* r, const void* boxes_v, int n_boxes, const vo
     }
     r->n_fast = p.n_fast;
     r->fast_flat = p.fast_flat;
-    r->bvh.fast_flat = ((r->debug_flags >> 11) & 1) ? 0 : r->fast_flat;
+    r->bvh.fast_flat = flat_walk(r);
     r->n_mats = n_mats; r->light_count = light_count; r->cam = p.cam;
     r->cam_tris = p.cam_tris;
     r->n_top = p.n_top;
@@ -1717,6 +1722,7 @@ int cl2_query_organisation(cl2_renderer* r, cl2_organisation* out) {
     out->wide_connections = (wide_walk(r) && split_conn(r)) ? 1 : 0;
     out->tree_bytes = (int64_t)r->bvh.n_nodes * 32 + (int64_t)r->bvh.n_tris * 48;
     out->sample_streams = r->streams;
+    out->staged_bytes = (int32_t)bvh_lds_bytes(r);
     return CL2_OK;
 }
 /* Child order of the 4-wide walks (round 6).  0 (default) = the reference's fixed order (trace.metal:157-160): bit-exact.  1 = the
@@ -1744,7 +1750,7 @@ int cl2_set_debug_flags(cl2_renderer* r, int flags) {
     if (((flags >> 4) & 7) != 0 && ((flags >> 4) & 7) != 7) return fail(r, CL2_E_INVALID, "debug bits 4-6 must be 0 or 7");
     r->debug_flags = flags;
     r->bvh.n_fast_nodes = ((flags >> 7) & 1) ? 0 : r->n_fast;      // bit 7: walk the full table (A/B of the pruned one)
-    r->bvh.fast_flat = ((flags >> 11) & 1) ? 0 : r->fast_flat;     // bit 11: per-lane walk of a flat pruned table (A/B of the wave-uniform one)
+    r->bvh.fast_flat = flat_walk(r);     // bit 11: per-lane walk of a flat pruned table (A/B of the wave-uniform one); bit 26: its clamped loop
     return CL2_OK;
 }
 /* Reproducible light image (off by default): the t = 1 contributions are written as records, sorted by (target pixel, s, source

@@ -7,6 +7,7 @@ namespace cl2 {
 
 constexpr int LDS_NODE_CAP = 512;   // records in the LDS window: at most 512 * 32 B = 16 KB
 constexpr int LDS_TRI_CAP = 512;    // triangles staged in LDS when the whole scene has no more: at most 512 * 48 B = 24 KB
+constexpr int LDS_TRI_PADS = 2;     // pad records behind the staged triangles: fetched by the flat walk, never tested (bvh_traverse.hpp)
 constexpr int LEAF_PACK_MAX = 16;   // triangles per leaf record
 constexpr int WIDE_EMPTY = (int)0x80000000;   // ref of an empty slot of a wide node (bvh_wide.hpp)
 constexpr int SHADE_LDS_CAP = 128;  // shading triangles staged in LDS by the subpath kernel (64 B each)

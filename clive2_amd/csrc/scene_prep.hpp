@@ -260,8 +260,9 @@ inline void build_fast(const Scene& s, const Order& o, PreparedScene& out) {
     // LDS budget: the pruned table sits beside the full one (rays with a non-finite 1/d need that) in every workgroup that stages
     // the tree.  Three such workgroups per CU (160 KB) is what the subpath kernel runs at with its 9.7 KB of static shading
     // tables; a scene near the 512-record / 512-triangle caps would lose a workgroup per CU to the extra table (and a
-    // 64-KB-per-workgroup part would refuse the launch), so there it is not built.
-    const size_t lds_with_fast = ((size_t)2 * n_records + (size_t)3 * s.n_tris + (size_t)2 * n_fast) * sizeof(float4) + sizeof(ShadeLds);
+    // 64-KB-per-workgroup part would refuse the launch), so there it is not built.  The staged triangles end in LDS_TRI_PADS pad
+    // records (bvh_traverse.hpp: stage_bvh).
+    const size_t lds_with_fast = ((size_t)2 * n_records + (size_t)3 * (s.n_tris + LDS_TRI_PADS) + (size_t)2 * n_fast) * sizeof(float4) + sizeof(ShadeLds);
     if (n_fast == n_records || lds_with_fast > (size_t)160 * 1024 / 3) return;
     out.n_fast = n_fast;
     out.fast_flat = 1;

@@ -28,6 +28,20 @@ __device__ __forceinline__ float rcp_exact(float a) {
     }
     return 1.0f / a;
 }
+// The same window test in two vector instructions instead of three (field extract, add, compare).  Shifting the sign out puts
+// the exponent field e into the top byte; adding -(1 << 24) then wraps e = 0 above every accepted value, and the 24 bits below
+// the exponent cannot carry into the comparison with 252 << 24: one v_lshl_add_u32 and one compare.  Same decision for all 2^32
+// patterns (tools/rcp_window_check.hip runs them), so rcp_exact_w(a) is rcp_exact(a) bit for bit.  The bias lives in a register
+// (a VOP3 operand cannot be a literal): the form pays where that register is amortised over a loop -- the flat walk's triangle
+// tests -- and costs a VGPR elsewhere (the 4-wide walks at 64 VGPRs would spill), so rcp_exact keeps the field form.
+__host__ __device__ __forceinline__ bool rcp_window(unsigned bits) { return (bits << 1) + 0xFF000000u < 0xFC000000u; }
+__device__ __forceinline__ float rcp_exact_w(float a) {
+    if (rcp_window(__float_as_uint(a))) {
+        const float r = __builtin_amdgcn_rcpf(a);
+        return __builtin_fmaf(__builtin_fmaf(-a, r, 1.0f), r, r);
+    }
+    return 1.0f / a;
+}
 constexpr float PI_CONST = 3.14159265359f;           // trace.metal:4
 __device__ __forceinline__ float div_pi(float x) {
     const unsigned e = (__float_as_uint(x) >> 23) & 0xFFu;

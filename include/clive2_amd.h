@@ -265,7 +265,7 @@ typedef struct {
                                        dropped: exact for rays with finite 1/d); 0: none */
     int64_t tree_bytes;             /* 32 B per record + 48 B per intersection triangle */
     int32_t sample_streams;         /* cl2_set_sample_streams */
-    int32_t reserved;
+    int32_t staged_bytes;         /* dynamic LDS of a launch that stages the tree: records, triangles with their pad records, pruned table */
 } cl2_organisation;
 int cl2_query_organisation(cl2_renderer* r, cl2_organisation* out);
 
@@ -302,11 +302,14 @@ int cl2_read_walk_tallies(cl2_renderer* r, cl2_walk_tallies* out);
  *   bit 25      connection rays of a tree wholly staged in LDS with a flat pruned table: the set-up launch and the walk
  *               launch over a global tag queue (csrc/kernels.hpp: k_connect_setup, k_traverse_conn) instead of the fused
  *               launch with a workgroup-local queue (k_connect_walk_lds), for A/B runs and tests
+ *   bit 26      flat pruned table of an LDS-resident tree (closest_hit_flat): the loop with the next-record index clamped on the
+ *               scalar unit and the leaf record read in three steps (closest_hit_flat_clamped) instead of the one that keeps the
+ *               record address in a vector register and fetches past the last triangle into pad records, for A/B runs and tests
  * Any other bit is refused (CL2_E_INVALID).  Bits 0-2 exist ONLY in the test variant of the library
  * (libclive2_amd_test.so, -DCL2_TEST_VARIANT), where they switch parts of the resolve stage off for timing
  * dissections -- bit 0 the t = 1 splat atomics, bit 1 / bit 2 the t >= 2 / t == 1 strategy pairs -- and make the
  * render INVALID; the shipped library refuses them. */
-#define CL2_DEBUG_KNOWN_BITS 0x02FF7FFF
+#define CL2_DEBUG_KNOWN_BITS 0x06FF7FFF
 int cl2_set_debug_flags(cl2_renderer* r, int flags);
 /* Reproducible light image, off by default.  The reference's light-image chain (sort by target pixel, per-pixel gather:
  * src/renderer.py:97-111, :213-250, src/trace.metal:872-964) is deterministic; the float atomics that replace it add a pixel's

@@ -8,7 +8,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COUNTERS = ("SQ_INSTS_VALU", "TCP_TOTAL_CACHE_ACCESSES_sum")
+COUNTERS = ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "TCP_TOTAL_CACHE_ACCESSES_sum")
 # r08: the accumulate kernels became templates on MOMENTS; the render runs the <false> instantiations
 # r11: the camera-ray generator and the resolve kernel gained a MAPPED parameter (adaptive sampling); the render runs <false>
 # r14: the accumulate kernels gained a BUCKETS parameter (robust picture); the render runs <false,false>

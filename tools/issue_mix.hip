@@ -62,6 +62,19 @@ __global__ __launch_bounds__(256) void k(float* out, int iters, float seed) {
                          V8 "ds_read_b96 v[40:42], %10\n ds_read_b96 v[44:46], %10 offset:16\n ds_read_b96 v[48:50], %10 offset:32\n s_waitcnt lgkmcnt(0)\n"
                          : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(m), "v"(c), "v"(0)
                          : "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51");
+        } else if (MODE == 9 || MODE == 10) {
+            // the scalar side of the flat LDS walk's triangle loop (bvh_traverse.hpp, closest_hit_flat) per 32 vector instructions:
+            // three exec-mask regions with a not-taken s_cbranch_execz, waits, and the loop's own scalar ALU work -- MODE 9 as the
+            // clamped loop has it (144 vector : 42 scalar ALU : 24 waits and branches per trip = 32 : 9.3 : 5.3), MODE 10 as the
+            // loop with the address in a vector register has it (141 : 33 : 26 = 32 : 7.5 : 5.9)
+#define REGION(L) "s_and_saveexec_b64 s[20:21], exec\n s_cbranch_execz " L "f\n" V8 L ": s_or_b64 exec, exec, s[20:21]\n"
+            if (MODE == 9)
+                asm volatile(REGION("1") "s_add_u32 s22, s22, 1\n s_waitcnt lgkmcnt(0)\n" REGION("2") "s_add_u32 s23, s23, 1\n s_waitcnt lgkmcnt(0)\n"
+                             REGION("3") "s_add_u32 s22, s22, 1\n" V8 OPS : "s20", "s21", "s22", "s23", "scc");
+            else
+                asm volatile(REGION("1") "s_add_u32 s22, s22, 1\n s_waitcnt lgkmcnt(0)\n" REGION("2") "s_waitcnt lgkmcnt(0)\n"
+                             REGION("3") "s_waitcnt lgkmcnt(0)\n" V8 OPS : "s20", "s21", "s22", "s23", "scc");
+#undef REGION
         }
     }
     out[blockIdx.x * 256 + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;
@@ -92,5 +105,7 @@ int main() {
     run<6>(d, "32 v_fma + 8 v_cmp + 8 s_and");
     run<7>(d, "32 v_fma + 12 ds_read_b128 (broadcast) + 1 wait");
     run<8>(d, "32 v_fma + 12 ds_read_b96 (broadcast) + 1 wait");
+    run<9>(d, "32 v_fma + flat walk's scalar side, clamped loop (9 SALU, 3 branches, 2 waits)");
+    run<10>(d, "32 v_fma + flat walk's scalar side, vector address (7 SALU, 3 branches, 3 waits)");
     return 0;
 }
