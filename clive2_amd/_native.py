@@ -96,6 +96,7 @@ EXPORTS = [
     "cl2_set_robust_buckets", "cl2_get_robust_buckets", "cl2_read_buckets_packed", "cl2_write_buckets_packed", "cl2_robust_picture",
     "cl2_denoise_robust",
     "cl2_keep_picture", "cl2_kept_picture", "cl2_write_picture", "cl2_read_picture", "cl2_picture_log_sum", "cl2_picture_tone_map",
+    "cl2_set_connection_query", "cl2_get_connection_query", "cl2_connection_query_active", "cl2_probe_visibility",
 ]
 
 
@@ -156,6 +157,10 @@ def lib(variant=None):
         L.cl2_get_sample_streams.argtypes = [C.c_void_p]
         L.cl2_set_traversal_order.argtypes = [C.c_void_p, C.c_int]
         L.cl2_get_traversal_order.argtypes = [C.c_void_p]
+        L.cl2_set_connection_query.argtypes = [C.c_void_p, C.c_int]
+        L.cl2_get_connection_query.argtypes = [C.c_void_p]
+        L.cl2_connection_query_active.argtypes = [C.c_void_p]
+        L.cl2_probe_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cl2_set_export_stream.argtypes = [C.c_void_p, C.c_int]
         L.cl2_comm_info.argtypes = [C.c_void_p, C.POINTER(CommInfo)]
         L.cl2_tone_log_sum.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]

@@ -230,6 +230,28 @@ __device__ __forceinline__ bool tri_test_branchless_tie(V3 o, V3 d, const float4
     return tie;
 }
 
+// tri_test_branchless_tie with a switch, for the seeded walk (bvh_wide.hpp, VIS): a test that is switched off changes nothing and
+// reports no tie -- the second triangle of a pair whose first one already blocks the lane, or the record behind an odd leaf's last
+// triangle -- without a copy of the held hit to fall back on.
+__device__ __forceinline__ bool tri_test_branchless_tie_if(bool enable, V3 o, V3 d, const float4& p0, const float4& p1, const float4& p2, int index, Hit& best) {
+    const V3 e1 = v3(p1), e2 = v3(p2);
+    const V3 h = cross(d, e2);
+    const float f = rcp_exact(dot(e1, h));
+    const V3 sv = o - v3(p0);
+    const float u = f * dot(sv, h);
+    const V3 q = cross(sv, e1);
+    const float v = f * dot(d, q);
+    const float t = f * dot(e2, q);
+    const bool inside = enable && !(u < 0 || u > 1) && !(v < 0 || u + v > 1) && t > DELTA_F;
+    const bool ok = inside && t < best.t;
+    const bool tie = inside && t == best.t;
+    best.tri = ok ? index : best.tri;
+    best.t = ok ? t : best.t;
+    best.u = ok ? u : best.u;
+    best.v = ok ? v : best.v;
+    return tie;
+}
+
 // The pruned table of a tiny scene (the Cornell box: three leaves, 16 triangles) has no inner records left: every ray
 // visits record 0, 1, 2, ... in that order, whatever it hits.  The per-lane walk above then spends vector instructions on
 // bookkeeping that is the same in every lane (record index, triangle index, loop tests, LDS addresses) and waits for each

@@ -64,7 +64,7 @@ struct WideView {
     int ovf_stride;            // entries per lane: the deepest stack the uploaded tree can produce (<= WIDE_STACK_OVERFLOW)
     int stack_lds;             // stack entries kept in LDS per lane (<= WIDE_STACK_LDS)
     int n_lds_nodes;           // wide nodes [0, n_lds_nodes) (breadth-first numbering: the top of the tree) staged in LDS
-    const int* tri_rank;       // ORDER only: each triangle's position in the reference's visit order; read when two hits tie at exactly one t
+    const int* tri_rank;       // ORDER, VIS: each triangle's position in the reference's visit order; read when two hits tie at exactly one t
 };
 
 // Round 4: the pass rewritten for its instruction count.  The ISA of round 3's loop showed what a pass paid beside its arithmetic:
@@ -130,7 +130,27 @@ struct WalkTally { unsigned visits = 0, tri_records = 0, spills = 0, bin_nodes =
 // holds best_t > t_x >= tmin: entered) and so does this walk (best_t >= t_x >= tmin: entered under `<=`; the tie rule keeps x).
 // tests/test_gpu_round6.py, test_gpu_fullsize.py: no differing ray is a tie, every differing ray is such a hit (2 / 3 / 5 rays of
 // 3.4e8 on configs 3 / 4 / 5).
-template <int TRI_REPS, bool TALLY, bool SPEC, bool PACK, bool ORDER, class Source>
+// VIS (cl2_set_connection_query(1), cl2_probe_visibility; opt-in, never the default and never the parity path): a ray may carry a
+// TARGET triangle T, and all that is asked is whether T is what the ray sees -- the one bit the resolve stage reads of a t >= 2
+// connection ray.  With hit(X) = tri_test_branchless' (ok, t), the ray is VISIBLE iff hit(T) is ok, with distance t_T, and no triangle
+// X != T of an ENTERED leaf is a BLOCKER:
+//   * a leaf is entered iff its own box passes `tmin <= tmax && tmin <= t_T` (the slab test, `<=` as ORDER uses);
+//   * X is a blocker iff hit(X) is ok and t_X < t_T, or t_X == t_T and tri_rank[X] < tri_rank[T] (the reference's first-met-wins).
+// Such a lane is SEEDED: T is tested first (one record), best = {T, t_T}, and the walk starts from there -- it prunes with the
+// target's distance from the root on and retires at the first blocker it holds.  The verdict does not depend on the visit order
+// (rays with finite 1/d): until the lane retires best_t STAYS at t_T, so every box is tested against the same value whenever it is
+// met; boxes nest (scene_prep.hpp), so a leaf that passes `tmin <= t_T` has ancestors that pass it (their tmin is <=, their tmax
+// >=), i.e. the walk reaches exactly the leaves the definition calls entered, and whether one of their triangles is a blocker is a
+// property of that triangle alone.  (WHICH blocker is stored depends on the order: the first one met in the reference's fixed
+// child order -- deterministic per ray.)  The verdict equals the reference's `closest_hit == T` except where a hit lies in front of
+// its own leaf box's entry distance -- the order dependence ORDER documents above: a blocker in a leaf with tmin > t_T is not
+// seen here, T or the closest hit in front of its leaf's tmin may be skipped there.
+// The slots are taken in the reference's fixed order (no sort network), so the stack bound computed at upload -- a static property
+// of the tree, whichever boxes pass -- still holds and the overflow array needs no resizing.  UNSEEDED lanes (target < 0: the six
+// t = 1 slots, whose distance the film projection needs; every ray with a non-finite 1/d, which takes the binary walk) run exactly
+// the closest-hit code: `<` tests, plain update, same bytes as without VIS.  A seeded lane is marked by node == n_nodes + 1
+// (`node` is otherwise unused by a lane of the wide walk): no register of its own.
+template <int TRI_REPS, bool TALLY, bool SPEC, bool PACK, bool ORDER, bool VIS, class Source>
 __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, const BvhView& b, unsigned n, unsigned* work_counter, const Source& src, WalkTally& tally) {
     constexpr bool TWO_TRIS = true;
     extern __shared__ float4 cl2_tree_lds[];
@@ -159,6 +179,9 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
     const int n_nodes = b.n_nodes;
     int key = 0;                               // the source's token of the lane's ray (pixel id / tag): store() needs it again
 
+    static_assert(!(VIS && ORDER), "the seeded walk keeps the reference's child order");
+    // VIS: a seeded lane (node == n_nodes + 1) tests boxes with `<=` -- a hit at exactly t_T still matters -- an unseeded one with `<`
+#define CL2_VIS_IN_FRONT(T) (node > n_nodes ? (T) <= best.t : (T) < best.t)
     auto take = [&](int ref) {                 // a stack entry / slot reference becomes the lane's next piece of work
         if (ref >= 0) cur = ref;
         else { const int info = ~ref; tri_i = info >> 4; tri_end = tri_i + (info & 15) + 1; }
@@ -173,7 +196,10 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
                 int ref, tbits;
                 if (sp < WIDE_S) { const int2 e = s_stack[sp * NT]; ref = e.x; tbits = e.y; }
                 else { ref = ovf[2 * (sp - WIDE_S)]; tbits = ovf[2 * (sp - WIDE_S) + 1]; }
-                if (ORDER ? __int_as_float(tbits) <= best.t : __int_as_float(tbits) < best.t) { take(ref); need = false; }
+                bool keep;                                  // (`if constexpr`: a mention of `node` here would make the closure capture it)
+                if constexpr (VIS) keep = CL2_VIS_IN_FRONT(__int_as_float(tbits));
+                else keep = ORDER ? __int_as_float(tbits) <= best.t : __int_as_float(tbits) < best.t;
+                if (keep) { take(ref); need = false; }
                 else need = sp > 0;
             }
         }
@@ -195,21 +221,37 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
             const unsigned avail = w_end - w_next;
             const unsigned rank = rank_below(idle);
             if (!active && rank < avail) {
-                key = src.load(w_next + rank, o, d);
+                [[maybe_unused]] int target = -1;
+                if constexpr (VIS) key = src.load(w_next + rank, o, d, target);
+                else key = src.load(w_next + rank, o, d);
                 inv = rcp3(d);
                 best = Hit{-1, __builtin_inff(), 0.0f, 0.0f};
                 cur = -1; tri_i = 0; tri_end = 0; sp = 0;
                 wlane = finite3(inv);
                 node = wlane ? n_nodes : 0;
                 active = true;
-                if (wlane) {
-                    // the root box, trace.metal:150-156 with best_t = inf
+                [[maybe_unused]] bool missed = false;
+                if constexpr (VIS) if (wlane && (unsigned)target < (unsigned)b.n_tris) {
+                    // the target first: missed -> the lane stores -1 and retires at the end of this pass; hit -> the lane is seeded
+                    if (PACK) {
+                        const float* __restrict__ tt = w.tris36 + (size_t)9 * target;
+                        tri_test_branchless(o, d, make_float4(tt[0], tt[1], tt[2], 0.0f), make_float4(tt[3], tt[4], tt[5], 0.0f), make_float4(tt[6], tt[7], tt[8], 0.0f), target, best);
+                    } else {
+                        const float4* __restrict__ tt = w.tris + (size_t)3 * target;
+                        tri_test_branchless(o, d, tt[0], tt[1], tt[2], target, best);
+                    }
+                    if (TALLY) tally.tri_records++;
+                    missed = best.tri < 0;
+                    node = missed ? node : n_nodes + 1;
+                }
+                if (VIS ? wlane && !missed : wlane) {
+                    // the root box, trace.metal:150-156 with best_t = inf (a seeded lane: t_T)
                     const float t0x = (w.root_lo.x - o.x) * inv.x, t0y = (w.root_lo.y - o.y) * inv.y, t0z = (w.root_lo.z - o.z) * inv.z;
                     const float t1x = (w.root_hi.x - o.x) * inv.x, t1y = (w.root_hi.y - o.y) * inv.y, t1z = (w.root_hi.z - o.z) * inv.z;
                     const float tmin = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t0x, t1x), __builtin_fminf(t0y, t1y)),
                                                        __builtin_fmaxf(__builtin_fminf(t0z, t1z), 0.0f));
                     const float tmax = __builtin_fminf(__builtin_fmaxf(t0x, t1x), __builtin_fminf(__builtin_fmaxf(t0y, t1y), __builtin_fmaxf(t0z, t1z)));
-                    if (tmin <= tmax && tmin < best.t) cur = 0;
+                    if (tmin <= tmax && (VIS ? CL2_VIS_IN_FRONT(tmin) : tmin < best.t)) cur = 0;
                 }
             }
             const unsigned taken = __popcll(idle) < avail ? __popcll(idle) : avail;
@@ -250,7 +292,7 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
                 const int2 e = s_stack[(sp - 1) * NT];
                 if (e.x >= 0) {                                             // a wide node on top: it leaves the stack, pruned or expanded
                     sp--;
-                    spec = ORDER ? __int_as_float(e.y) <= best.t : __int_as_float(e.y) < best.t;
+                    spec = VIS ? CL2_VIS_IN_FRONT(__int_as_float(e.y)) : (ORDER ? __int_as_float(e.y) <= best.t : __int_as_float(e.y) < best.t);
                     spec_ref = e.x;
                 }
             }
@@ -303,7 +345,7 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
                     tm[k] = tmin;
                     // an empty slot's box lies at +inf: never.  (ORDER: `<=`, so that a leaf that may hold a hit at exactly best_t is still
                     // entered -- the tie rule then decides as the reference does; an empty slot goes by its reference, below)
-                    pass[k] = tmin <= tmax && (ORDER ? tmin <= best.t : tmin < best.t);
+                    pass[k] = tmin <= tmax && (VIS ? CL2_VIS_IN_FRONT(tmin) : (ORDER ? tmin <= best.t : tmin < best.t));
                 }
                 if (ORDER) {
                     // nearest first: slots that do not pass sort behind all that do (key +inf, no reference); adjacent
@@ -367,9 +409,19 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
 #ifdef CL2_WALK_HISTO
                 if (rep == 0) h_t0 = true; else h_t1 = true;
 #endif
-                const int i0 = tri_i;
-                const int i1 = (TWO_TRIS && i0 + 1 < tri_end) ? i0 + 1 : i0;
+                int i0 = tri_i;
+                int i1 = (TWO_TRIS && i0 + 1 < tri_end) ? i0 + 1 : i0;
                 tri_i = i1 + 1;
+                if constexpr (VIS) {
+                    // A seeded lane holds T (best.tri, until it is blocked -- and then it has retired): T's record need not be read
+                    // again in its leaf.  T first of the pair: the pair starts behind it; T second: the first is tested alone.  (T
+                    // alone at the end of its leaf is tested again: it cannot pass `t < t_T`, and its tie with itself is none.)
+                    const int held = node > n_nodes ? best.tri : -2;
+                    i0 += (i0 == held && i0 + 1 < tri_end) ? 1 : 0;
+                    const bool more = i0 + 1 < tri_end;
+                    i1 = (more && i0 + 1 != held) ? i0 + 1 : i0;
+                    tri_i = (more && i0 + 1 == held) ? i0 + 2 : i1 + 1;
+                }
                 if (TALLY) tally.tri_records += (i1 != i0) ? 2u : 1u;
                 if (PACK) {
                     // the pair as ONE run of 72 bytes (five loads instead of six: what binds this walk is the L1's look-up rate, one
@@ -380,7 +432,24 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
                     float a[18];
 #pragma unroll
                     for (int k = 0; k < 18; k++) a[k] = ta[k];
-                    if (ORDER) {
+                    if (VIS) {
+                        // a seeded lane holds T until it meets a blocker, keeps the FIRST blocker it meets, and settles a hit at exactly
+                        // t_T by the reference's rule (T's tie with itself is none); an unseeded lane: the plain tests, ties ignored
+                        const bool sd = node > n_nodes;
+                        const int held = best.tri;
+                        bool tie = tri_test_branchless_tie(o, d, make_float4(a[0], a[1], a[2], 0.0f), make_float4(a[3], a[4], a[5], 0.0f), make_float4(a[6], a[7], a[8], 0.0f), i0, best) && sd && i0 != held;
+                        tie = (tri_test_branchless_tie_if(i1 != i0 && !(sd && best.tri != held), o, d, make_float4(a[9], a[10], a[11], 0.0f), make_float4(a[12], a[13], a[14], 0.0f),
+                                                          make_float4(a[15], a[16], a[17], 0.0f), i0 + 1, best) && sd) || tie;
+                        if (__any(tie)) {
+                            if (tie && best.tri == held) {
+                                const float* __restrict__ tr = w.tris36 + (size_t)9 * i0;
+                                tri_test_tie_rule(o, d, make_float4(tr[0], tr[1], tr[2], 0.0f), make_float4(tr[3], tr[4], tr[5], 0.0f), make_float4(tr[6], tr[7], tr[8], 0.0f), i0, best, w.tri_rank);
+                                if (i1 != i0 && best.tri == held)
+                                    tri_test_tie_rule(o, d, make_float4(tr[9], tr[10], tr[11], 0.0f), make_float4(tr[12], tr[13], tr[14], 0.0f), make_float4(tr[15], tr[16], tr[17], 0.0f), i1, best, w.tri_rank);
+                            }
+                        }
+                        if (sd && best.tri != held) { cur = -1; sp = 0; tri_i = tri_end; }       // blocked: retire
+                    } else if (ORDER) {
                         bool tie = tri_test_branchless_tie(o, d, make_float4(a[0], a[1], a[2], 0.0f), make_float4(a[3], a[4], a[5], 0.0f), make_float4(a[6], a[7], a[8], 0.0f), i0, best);
                         Hit second = best;
                         const bool tie2 = tri_test_branchless_tie(o, d, make_float4(a[9], a[10], a[11], 0.0f), make_float4(a[12], a[13], a[14], 0.0f), make_float4(a[15], a[16], a[17], 0.0f), i0 + 1, second);
@@ -407,7 +476,19 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
                     const float4 a0 = ta[0], a1 = ta[1], a2 = ta[2];
                     float4 c0, c1, c2;
                     if (TWO_TRIS) { c0 = tb[0]; c1 = tb[1]; c2 = tb[2]; }
-                    if (ORDER) {
+                    if (VIS) {
+                        const bool sd = node > n_nodes;
+                        const int held = best.tri;
+                        bool tie = tri_test_branchless_tie(o, d, a0, a1, a2, i0, best) && sd && i0 != held;
+                        tie = (tri_test_branchless_tie_if(i1 != i0 && !(sd && best.tri != held), o, d, c0, c1, c2, i1, best) && sd) || tie;
+                        if (__any(tie)) {
+                            if (tie && best.tri == held) {
+                                tri_test_tie_rule(o, d, ta[0], ta[1], ta[2], i0, best, w.tri_rank);
+                                if (i1 != i0 && best.tri == held) tri_test_tie_rule(o, d, tb[0], tb[1], tb[2], i1, best, w.tri_rank);
+                            }
+                        }
+                        if (sd && best.tri != held) { cur = -1; sp = 0; tri_i = tri_end; }       // blocked: retire
+                    } else if (ORDER) {
                         bool tie = tri_test_branchless_tie(o, d, a0, a1, a2, i0, best);
                         if (TWO_TRIS) tie = (tri_test_branchless_tie(o, d, c0, c1, c2, i1, best) && i1 != i0) || tie;   // (an odd leaf's last triangle is tested twice: no tie)
                         if (__any(tie)) {
@@ -441,6 +522,7 @@ __device__ __forceinline__ void traverse_wide_persistent(const WideView& w, cons
         }
 #endif
     }
+#undef CL2_VIS_IN_FRONT
 }
 
 }  // namespace cl2

@@ -300,6 +300,30 @@ struct ConnRaySource {          // connection rays: tag {slot, pixel} -> light v
     }
 };
 
+// Sources of the seeded walk (bvh_wide.hpp, VIS): load() also yields the ray's target triangle, < 0 for "unseeded" (plain closest hit).
+// Connection rays: the camera vertex's triangle for the t >= 2 slots -- what the resolve stage compares the stored triangle with
+// (load_camera_vertex, connect_resolve.hpp) -- and -1 for the six t = 1 slots, whose distance the film projection needs.
+struct ConnVisRaySource {
+    ConnRaySource conn; const int* ctri;           // ctri: the camera paths' tri[MAX_VERTS][B]
+    __device__ __forceinline__ int load(unsigned j, V3& o, V3& d, int& target) const {
+        const int tag = conn.load(j, o, d);
+        const int pid = tag & ((1 << TAG_PID_BITS) - 1), slot = (unsigned)tag >> TAG_PID_BITS;
+        target = slot < MAX_VERTS ? -1 : ctri[(size_t)(slot / 6) * conn.B + pid];
+        return tag;
+    }
+    __device__ __forceinline__ void store(int tag, const Hit& h) const { conn.store(tag, h); }
+};
+struct ProbeVisRaySource {      // cl2_probe_visibility: ray j = (o[j], d[j]) with target[j]; hit[j] as PathRaySource stores it
+    const float4* o4; const float4* d4; const int* target; float4* hit;
+    __device__ __forceinline__ int load(unsigned j, V3& o, V3& d, int& tgt) const {
+        o = v3(o4[j]); d = v3(d4[j]); tgt = target[j];
+        return (int)j;
+    }
+    __device__ __forceinline__ void store(int j, const Hit& h) const {
+        hit[j] = make_float4(__int_as_float(h.tri), h.t, h.u, h.v);
+    }
+};
+
 // SGPR budget: 256-thread workgroups are admitted per CU up to floor(800 / (ceil(sgprs / 16) * 16 + 16)) -- 8 up to 80
 // SGPRs, 7 from 81 (MI355X_MICROARCH.md, "Residency").  Left alone the compiler takes 81 for the connection-ray
 // instantiation: one workgroup in eight of the persistent grid then never becomes resident beside the others.
@@ -330,7 +354,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(78))) void k_
 // (The ray tally is added BEFORE the walk: `threadIdx.x == 0` after it would keep the thread index alive through the whole loop,
 // in a kernel held to 64 VGPRs -- round 4's builds spilled exactly that register to scratch at entry and reloaded it at exit.)
 // The tallying variant (cl2_set_counting(2), never timed) carries four more counters per lane and takes 6 waves per SIMD.
-template <int TRI_REPS, class Source, bool TALLY = false, bool SPEC = false, bool PACK = false, bool ORDER = false>
+template <int TRI_REPS, class Source, bool TALLY = false, bool SPEC = false, bool PACK = false, bool ORDER = false, bool VIS = false>
 __global__ __launch_bounds__(BLOCK, TALLY ? 6 : 8) __attribute__((amdgpu_num_sgpr(80))) void k_traverse_wide(WideView wide, BvhView bvh, const unsigned* __restrict__ count,
                                                         unsigned* __restrict__ work_counter, Source src, Stats* stats, int is_conn) {
     const unsigned n = *count;
@@ -340,7 +364,7 @@ __global__ __launch_bounds__(BLOCK, TALLY ? 6 : 8) __attribute__((amdgpu_num_sgp
         if (TALLY) atomicAdd(&stats->walk[is_conn ? 1 : 0][0], (unsigned long long)n);
     }
     WalkTally tally;
-    traverse_wide_persistent<TRI_REPS, TALLY, SPEC, PACK, ORDER>(wide, bvh, n, work_counter, src, tally);
+    traverse_wide_persistent<TRI_REPS, TALLY, SPEC, PACK, ORDER, VIS>(wide, bvh, n, work_counter, src, tally);
     if (TALLY) {
         unsigned v[4] = {tally.visits, tally.tri_records, tally.spills, tally.bin_nodes};
         for (int off = 32; off > 0; off >>= 1)

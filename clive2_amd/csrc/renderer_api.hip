@@ -16,6 +16,7 @@
 #include <chrono>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/clive2_amd.h"
@@ -87,7 +88,8 @@ struct cl2_renderer {
     // 4-wide collapse of the tree for the exact wide walk (bvh_wide.hpp); n_wide == 0: not available for this scene
     float4* d_wide = nullptr;
     int n_wide = 0;
-    int* d_tri_rank = nullptr;           // ORDER: each triangle's position in the reference's visit order (exact-t ties; bvh_wide.hpp)
+    int connection_query = 0;            // 0 = connection rays are closest-hit queries; 1 = the t >= 2 ones are visibility queries seeded with their target (opt-in: bvh_wide.hpp VIS)
+    int* d_tri_rank = nullptr;           // ORDER, VIS: each triangle's position in the reference's visit order (exact-t ties; bvh_wide.hpp)
     float* d_tris36 = nullptr;           // 36-byte triangle records of a tree that streams from beyond L2 (bvh_wide.hpp, PACK); nullptr: none
     int n_fast = 0;                      // records of the pruned table (bvh.n_fast_nodes unless debug_flags bit 7 switches it off)
     CamTris cam_tris{0, {0, 0, 0, 0}};   // the triangles with is_camera set, as kernel arguments of the resolve stage (n < 0: too many, look them up)
@@ -353,6 +355,12 @@ inline bool wide_walk(const cl2_renderer* r) {
 // launch against 1.7 GB of vertices).  And a level launch of a 4K frame (8.3 M rays, 16 per lane) has little tail to
 // lose: there the per-level form wins in serial order too (interior 4K: 53.7 vs 61.6 ms of subpath time, blob 24.0 vs
 // 28.1).  So the automatic choice takes it in the serial order and up to 2^22 pixels only.
+// The connection launch really runs the seeded visibility walk (cl2_set_connection_query(1)): only where connection rays take
+// k_traverse_wide -- not in the fused or grid-stride launches of an LDS-resident tree, not without a wide collapse, not while the
+// reference walk's tallies are taken (count_ref: the binary walk).
+inline bool conn_vis(const cl2_renderer* r) {
+    return r->connection_query == 1 && !fused_conn(r) && split_conn(r) && wide_walk(r);
+}
 inline bool whole_subpaths(const cl2_renderer* r) {
     if (r->traversal_order != 0) return false;                       // nearest-first order exists in k_traverse_wide only: every ray goes through it
     if (r->counting == 2 && r->traversal_mode != 4) return false;   // the walk's own tallies are taken in k_traverse_wide: every ray goes through it
@@ -414,7 +422,8 @@ int ensure_wide_overflow(cl2_renderer* r) {
     return dev_alloc(r, &r->d_wide_ovf, 2 * lanes * (size_t)std::max(r->wide_ovf_entries, 1));
 }
 
-template <class Source>
+// VIS: the seeded visibility walk (bvh_wide.hpp) -- a source that yields targets; the speculative walk in the reference's child order only.
+template <class Source, bool VIS = false>
 // quiet: the feature pass (denoise.hpp) -- the rays go to its own tally, not to cl2_read_counters / cl2_read_walk_tallies
 int launch_wide(cl2_renderer* r, hipStream_t st, int stage, const unsigned* count, unsigned* work_counter, Source src, int is_conn,
                 bool quiet = false) {
@@ -448,17 +457,23 @@ int launch_wide(cl2_renderer* r, hipStream_t st, int stage, const unsigned* coun
     BvhView b = r->bvh;
     b.n_lds_nodes = 0; b.lds_tris = 0; b.n_fast_nodes = 0;
 #define CL2_WIDE(REPS, TALLY, SPEC, PACK, ORDER) \
-    hipLaunchKernelGGL((k_traverse_wide<REPS, Source, TALLY, SPEC, PACK, ORDER>), dim3(grid), dim3(BLOCK), lds, st, w, b, count, work_counter, src, stats, is_conn)
+    hipLaunchKernelGGL((k_traverse_wide<REPS, Source, TALLY, SPEC, PACK, ORDER, VIS>), dim3(grid), dim3(BLOCK), lds, st, w, b, count, work_counter, src, stats, is_conn)
 // (a macro argument may not be a run-time value: one dispatch level per template parameter)
 #define CL2_WIDE_BY_SPEC(REPS, TALLY, PACK) do { if (spec) CL2_WIDE(REPS, TALLY, true, PACK, false); else CL2_WIDE(REPS, TALLY, false, PACK, false); } while (0)
 #define CL2_WIDE_BY_TALLY(REPS, PACK) do { \
-        if (r->traversal_order != 0) { if (tally) CL2_WIDE(REPS, true, true, PACK, true); else CL2_WIDE(REPS, false, true, PACK, true); } \
+        if constexpr (VIS) { if (tally) CL2_WIDE(REPS, true, true, PACK, false); else CL2_WIDE(REPS, false, true, PACK, false); } \
+        else if (r->traversal_order != 0) { if (tally) CL2_WIDE(REPS, true, true, PACK, true); else CL2_WIDE(REPS, false, true, PACK, true); } \
         else if (tally) CL2_WIDE_BY_SPEC(REPS, true, PACK); else CL2_WIDE_BY_SPEC(REPS, false, PACK); } while (0)
-    const bool spec = !((r->debug_flags >> 13) & 1);            // speculative expansion of the stack top (bvh_wide.hpp); bit 13: off
+    [[maybe_unused]] const bool spec = !((r->debug_flags >> 13) & 1);            // speculative expansion of the stack top (bvh_wide.hpp); bit 13: off
     // 36-byte triangle records, a pair fetched as one run of 72 bytes (bvh_wide.hpp: PACK); bit 14: the 48-byte records of the other
     // walks.  The opt-in nearest-first child order (cl2_set_traversal_order; NOT the parity path) exists for the speculative walk only.
     const bool pack = w.tris36 && !((r->debug_flags >> 14) & 1);
-    if (streams_from_memory) { if (pack) CL2_WIDE_BY_TALLY(1, true); else CL2_WIDE_BY_TALLY(1, false); }
+    if constexpr (std::is_same_v<Source, ConnVisRaySource>) {
+        // the seeded connection launch exists for the tree's own record form only: bit 14 is an A/B switch of the closest-hit walk and
+        // is refused together with cl2_set_connection_query(1) (its 48-byte instantiation with one pair per pass would spill)
+        if (!pack) return fail(r, CL2_E_STATE, "the seeded connection walk reads the packed triangle records");
+        if (streams_from_memory) CL2_WIDE_BY_TALLY(1, true); else CL2_WIDE_BY_TALLY(WIDE_TRI_REPS, true);
+    } else if (streams_from_memory) { if (pack) CL2_WIDE_BY_TALLY(1, true); else CL2_WIDE_BY_TALLY(1, false); }
     else { if (pack) CL2_WIDE_BY_TALLY(WIDE_TRI_REPS, true); else CL2_WIDE_BY_TALLY(WIDE_TRI_REPS, false); }
 #undef CL2_WIDE_BY_TALLY
 #undef CL2_WIDE_BY_SPEC
@@ -612,7 +627,10 @@ int launch_connect(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs)
             HIP_TRY(r, hipMemsetAsync(r->d_work + 7 * WORK_STRIDE, 0, WORK_STRIDE * sizeof(unsigned), st));
             ConnRaySource src{r->d_ctag, lp.P0, cp.P0, r->d_chit[cs],
                               V3{r->cam.focal_point[0], r->cam.focal_point[1], r->cam.focal_point[2]}, B};
-            if (wide_walk(r)) {
+            if (conn_vis(r)) {
+                ConnVisRaySource vsrc{src, cp.tri};
+                TRY((launch_wide<ConnVisRaySource, true>(r, st, 1, r->d_qcount + 7, r->d_work + 7 * WORK_STRIDE, vsrc, 1)));
+            } else if (wide_walk(r)) {
                 TRY(launch_wide(r, st, 1, r->d_qcount + 7, r->d_work + 7 * WORK_STRIDE, src, 1));
             } else {
 #define CL2_PERSIST(CNT, TWO, SRCT, SRC)                                                                                  \
@@ -1733,12 +1751,32 @@ int cl2_query_organisation(cl2_renderer* r, cl2_organisation* out) {
 int cl2_set_traversal_order(cl2_renderer* r, int order) {
     if (!r) return CL2_E_INVALID;
     if (order != 0 && order != 1) return fail(r, CL2_E_INVALID, "traversal order must be 0 (reference order, exact) or 1 (nearest child first)");
+    if (order == 1 && r->connection_query == 1) return fail(r, CL2_E_INVALID, "the seeded connection query keeps the reference's child order: cl2_set_connection_query(0) first");
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
     r->traversal_order = order;
     return CL2_OK;
 }
 int cl2_get_traversal_order(const cl2_renderer* r) { return r ? r->traversal_order : CL2_E_INVALID; }
+/* What a connection ray asks of the tree.  0 (default) = its closest hit, as the reference.  1 = for a t >= 2 pair, whether the camera
+ * vertex's triangle is what the ray sees: the walk starts from the target's distance and stops at the first blocker (csrc/bvh_wide.hpp
+ * VIS).  Opt-in and NOT the parity path: the verdict is the reference's except where a hit lies in front of its own leaf box.  Applies
+ * where connection rays take the 4-wide walk (cl2_connection_query_active). */
+int cl2_set_connection_query(cl2_renderer* r, int mode) {
+    if (!r) return CL2_E_INVALID;
+    if (mode != 0 && mode != 1) return fail(r, CL2_E_INVALID, "connection query must be 0 (closest hit, exact) or 1 (seeded visibility walk)");
+    if (mode == 1 && r->traversal_order != 0) return fail(r, CL2_E_INVALID, "the seeded connection query keeps the reference's child order: cl2_set_traversal_order(0) first");
+    if (mode == 1 && (r->debug_flags & (3 << 13))) return fail(r, CL2_E_INVALID, "the seeded connection query has no form without the speculative expansion or the packed triangle records: clear debug bits 13 and 14 first");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    r->connection_query = mode;
+    return CL2_OK;
+}
+int cl2_get_connection_query(const cl2_renderer* r) { return r ? r->connection_query : CL2_E_INVALID; }
+int cl2_connection_query_active(const cl2_renderer* r) {
+    if (!r) return CL2_E_INVALID;
+    return (r->scene_ok && conn_vis(r)) ? 1 : 0;
+}
 int cl2_set_debug_flags(cl2_renderer* r, int flags) {
     if (!r) return CL2_E_INVALID;
 #ifndef CL2_TEST_VARIANT
@@ -1748,6 +1786,8 @@ int cl2_set_debug_flags(cl2_renderer* r, int flags) {
 #endif
     if (flags & ~CL2_DEBUG_KNOWN_BITS) return fail(r, CL2_E_INVALID, "unknown debug flag bits (see include/clive2_amd.h)");
     if (((flags >> 4) & 7) != 0 && ((flags >> 4) & 7) != 7) return fail(r, CL2_E_INVALID, "debug bits 4-6 must be 0 or 7");
+    if ((flags & (3 << 13)) && r->connection_query == 1)
+        return fail(r, CL2_E_INVALID, "debug bits 13 and 14 are A/B switches of the closest-hit walk; the seeded connection query has no such form: cl2_set_connection_query(0) first");
     r->debug_flags = flags;
     r->bvh.n_fast_nodes = ((flags >> 7) & 1) ? 0 : r->n_fast;      // bit 7: walk the full table (A/B of the pruned one)
     r->bvh.fast_flat = flat_walk(r);     // bit 11: per-lane walk of a flat pruned table (A/B of the wave-uniform one); bit 26: its clamped loop
@@ -1961,6 +2001,53 @@ int cl2_probe_traverse(cl2_renderer* r, const void* rays_v, size_t n_rays, int32
             best_t[i] = h[i].y; u[i] = h[i].z; v[i] = h[i].w;
         }
     dev_free(r, d_o); dev_free(r, d_d); dev_free(r, d_h); dev_free(r, d_n);
+    return rc;
+}
+
+int cl2_probe_visibility(cl2_renderer* r, const void* rays_v, size_t n_rays, const int32_t* target, int32_t* out_tri, float* out_t) {
+    STAGE_PROLOGUE(r);
+    if (!rays_v || !target || !out_tri || !out_t) return fail(r, CL2_E_INVALID, "NULL probe array");
+    if (r->n_wide <= 0) return fail(r, CL2_E_STATE, "the uploaded scene has no 4-wide collapse: no seeded walk");
+    if ((r->debug_flags >> 13) & 1) return fail(r, CL2_E_STATE, "the seeded walk exists for the speculative walk only: clear debug bit 13");
+    if (n_rays == 0) return CL2_OK;
+    if (n_rays > (size_t)1 << 30) return fail(r, CL2_E_INVALID, "too many probe rays");
+    for (size_t i = 0; i < n_rays; i++)
+        if (target[i] >= r->bvh.n_tris) return fail(r, CL2_E_INVALID, "probe target is not a triangle of the scene");
+    const RayRec* rays = static_cast<const RayRec*>(rays_v);
+    std::vector<float4> o(n_rays), d(n_rays), h(n_rays);
+    for (size_t i = 0; i < n_rays; i++) {
+        o[i] = make_float4(rays[i].origin[0], rays[i].origin[1], rays[i].origin[2], 0.0f);
+        d[i] = make_float4(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2], 0.0f);
+    }
+    float4 *d_o = nullptr, *d_d = nullptr, *d_h = nullptr;
+    int* d_t = nullptr;
+    unsigned* d_n = nullptr;
+    int rc = dev_alloc(r, &d_o, n_rays);
+    if (rc == CL2_OK) rc = dev_alloc(r, &d_d, n_rays);
+    if (rc == CL2_OK) rc = dev_alloc(r, &d_h, n_rays);
+    if (rc == CL2_OK) rc = dev_alloc(r, &d_t, n_rays);
+    if (rc == CL2_OK) rc = dev_alloc(r, &d_n, (size_t)1);
+    if (rc == CL2_OK) {
+        const unsigned n = (unsigned)n_rays;
+        bool ok = hipMemcpy(d_o, o.data(), n_rays * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(d_d, d.data(), n_rays * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(d_t, target, n_rays * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(d_n, &n, sizeof n, hipMemcpyHostToDevice) == hipSuccess;
+        if (!ok) rc = fail(r, CL2_E_HIP, "probe upload failed");
+    }
+    if (rc == CL2_OK && hipMemsetAsync(r->d_work, 0, WORK_STRIDE * sizeof(unsigned), r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "probe memset failed");
+    if (rc == CL2_OK) {
+        ProbeVisRaySource src{d_o, d_d, d_t, d_h};
+        rc = launch_wide<ProbeVisRaySource, true>(r, r->stream, 0, d_n, r->d_work, src, 0);
+        if (rc == CL2_OK) rc = drain(r);
+    }
+    if (rc == CL2_OK && hipMemcpy(h.data(), d_h, n_rays * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(r, CL2_E_HIP, "probe download failed");
+    if (rc == CL2_OK)
+        for (size_t i = 0; i < n_rays; i++) {
+            std::memcpy(&out_tri[i], &h[i].x, 4);
+            out_t[i] = h[i].y;
+        }
+    dev_free(r, d_o); dev_free(r, d_d); dev_free(r, d_h); dev_free(r, d_t); dev_free(r, d_n);
     return rc;
 }
 

@@ -44,6 +44,10 @@ def main(argv=None):
     ap.add_argument("--reproducible", action="store_true",
                     help="sum the light image in a fixed order (Renderer.set_reproducible) instead of with float atomics: two runs "
                          "then write the same bytes, as the reference's sort + gather chain does (renderer.py:212-250); slower")
+    ap.add_argument("--visibility-query", action="store_true",
+                    help="walk the t >= 2 connection rays as visibility queries seeded with their target triangle "
+                         "(Renderer.set_connection_query(1), DESIGN.md 6.10): opt-in, not the parity path; no effect on scenes "
+                         "whose tree is resident in LDS, such as the Cornell box")
     ap.add_argument("--denoise", action="store_true",
                     help="after the samples, render the first-hit features and write the denoised picture (Renderer.denoised_image)")
     ap.add_argument("--feature-samples", type=int, default=4, help="camera rays per pixel of the feature pass of --denoise")
@@ -108,6 +112,8 @@ def main(argv=None):
     K = renderer.streams
     if args.reproducible:
         renderer.set_reproducible(True)
+    if args.visibility_query:
+        renderer.set_connection_query(1)
     if args.target_error is not None or args.error_out or args.variance_guided:
         renderer.set_error_tracking(True)
     if args.robust or args.robust_denoise:

@@ -466,6 +466,22 @@ class Renderer:
     def traversal_order(self):
         return int(self._L.cl2_get_traversal_order(self._h))
 
+    def set_connection_query(self, mode=1):
+        """What a connection ray asks of the tree (cl2_set_connection_query): 0 = its closest hit (the default, as the reference),
+        1 = for a t >= 2 pair, whether the camera vertex's triangle is what the ray sees -- a walk seeded with that triangle, which
+        prunes with its distance from the root on and stops at the first blocker.  Opt-in and NOT the parity path (the verdict
+        differs where a hit lies in front of its own leaf box: a few rays in 1e8); refused together with set_traversal_order(1)
+        and debug bits 13 / 14.  No reference counterpart."""
+        self._check(self._L.cl2_set_connection_query(self._h, int(mode)), "set_connection_query")
+
+    def connection_query(self):
+        return int(self._L.cl2_get_connection_query(self._h))
+
+    def connection_query_active(self):
+        """1 iff the uploaded scene's connection launch really runs the seeded walk (0 for an LDS-resident tree such as the Cornell
+        box, for a tree without a 4-wide collapse, and while set_counting(1) is on)."""
+        return int(self._L.cl2_connection_query_active(self._h))
+
     def set_reproducible(self, on=True):
         """Reproducible light image (cl2_set_reproducible): the t = 1 contributions sorted and summed in a fixed order instead of
         float atomics -- two renders of the same scene and seeds then agree byte for byte, as the reference's sort + gather
@@ -549,6 +565,20 @@ class Renderer:
         self._check(self._L.cl2_probe_traverse(self._h, ptr(rays), C.c_size_t(n), ptr(bi), ptr(bt), ptr(u), ptr(v)),
                     "probe_traverse")
         return bi, bt, u, v
+
+    def probe_visibility(self, rays, targets):
+        """Every ray through the seeded visibility walk with its target triangle (cl2_probe_visibility): per ray the stored triangle
+        and its distance -- (T, t_T) where the target is visible, the first blocker met where it is not, (-1, inf) where the ray
+        misses T; a target < 0 gives the plain closest hit."""
+        rays = np.ascontiguousarray(rays, dtype=st.Ray)
+        targets = np.ascontiguousarray(targets, dtype=np.int32)
+        n = len(rays)
+        if targets.shape != (n,):
+            raise ValueError("probe_visibility: one target per ray")
+        tri, t = np.empty(n, np.int32), np.empty(n, np.float32)
+        self._check(self._L.cl2_probe_visibility(self._h, ptr(rays), C.c_size_t(n), ptr(targets), ptr(tri), ptr(t)),
+                    "probe_visibility")
+        return tri, t
 
     # ---- denoiser (cl2_render_features / cl2_read_features / cl2_denoise, csrc/denoise.hpp) ----
     # settled on the Cornell box and the glass scene at 256 x 192, 4 samples, against 1024-sample pictures (include/clive2_amd.h)

@@ -334,6 +334,20 @@ int cl2_get_reproducible(const cl2_renderer* r);
  * either way).  No reference counterpart (src/trace.metal:144-176 has one order). */
 int cl2_set_traversal_order(cl2_renderer* r, int order);
 int cl2_get_traversal_order(const cl2_renderer* r);
+/* What a connection ray asks of the tree (additions to ABI 6).  mode = 0 (default): its closest hit, as the reference
+ * (src/trace.metal:144-176).  mode = 1: for a pair with t >= 2 the resolve stage reads one bit of that result -- whether the hit
+ * triangle is the camera vertex's triangle T -- so the ray becomes a VISIBILITY query seeded with T: T is tested first, the walk
+ * prunes with T's distance from the root on and stops at the first blocker (csrc/bvh_wide.hpp, VIS, has the definition and why it
+ * does not depend on the visit order).  The six t = 1 slots and rays with a zero direction component stay closest-hit queries,
+ * byte for byte.  NOT the reference's result by construction: the verdict differs where a hit lies in front of its own leaf box's
+ * entry distance, the order dependence cl2_set_traversal_order documents -- so: opt-in, never the default, never the parity path.
+ * Applies wherever connection rays take the 4-wide walk; cl2_connection_query_active says whether the uploaded scene's connection
+ * launch really runs the seeded walk (0 for a tree that is resident in LDS, for a tree without a 4-wide collapse, and while
+ * cl2_set_counting(1) is on).  Other modes are CL2_E_INVALID and leave the setting alone.  Refused (CL2_E_INVALID), whichever
+ * comes second: mode 1 with cl2_set_traversal_order(1), mode 1 with debug bit 13 or 14.  No reference counterpart. */
+int cl2_set_connection_query(cl2_renderer* r, int mode);
+int cl2_get_connection_query(const cl2_renderer* r);
+int cl2_connection_query_active(const cl2_renderer* r);
 /* Whole-subpath launch (traversal mode 4): lanes that must have gathered with a known closest hit before a wave runs
  * its bounce phase, and the steps the first of them waits at most.  0 = default (32 lanes, 48 steps).  Same results. */
 int cl2_set_subpath_gather(cl2_renderer* r, int lanes, int wait_steps);
@@ -358,7 +372,9 @@ int cl2_export_paths(cl2_renderer* r, int which, void* out_paths, size_t n_recor
 int cl2_export_aggregators(cl2_renderer* r, void* out, size_t n_records);                 /* 128-B stride */
 /* the connection stage's results of the last join_paths: per pixel the strategy-pair mask (bit (t-1)*6 + (s-1): the pair
  * passed the culls and has a ray), the closest-hit triangle of every pair (int32[36][n_pixels], slot-major; meaningful where
- * the mask bit is set) and the hit distance of the six t = 1 pairs (float[6][n_pixels]).  Any pointer may be NULL. */
+ * the mask bit is set) and the hit distance of the six t = 1 pairs (float[6][n_pixels]).  Any pointer may be NULL.
+ * Under cl2_set_connection_query(1), where it is active, `tri` of a t >= 2 pair holds the camera vertex's triangle T where T is
+ * visible and another value where it is not (the first blocker met, or -1 where the ray misses T): only `tri == T` means anything. */
 int cl2_export_connections(cl2_renderer* r, uint64_t* cmask, int32_t* tri, float* t1, size_t n_pixels);
 /* per-sample images: finalized_samples (float4), out_light_image rgb + summed light weight (float4),
  * sample_weights (K6 value only), out_camera_image (float4).  Any pointer may be NULL. */
@@ -373,6 +389,13 @@ int cl2_import_sample_images(cl2_renderer* r, const float* finalized4, const flo
  * kernel alone (src/trace.metal:144-176). */
 int cl2_probe_traverse(cl2_renderer* r, const void* rays, size_t n_rays, int32_t* best_i, float* best_t,
                        float* u, float* v);
+
+/* visibility probe: n rays as Ray records with one target triangle each, every ray through the seeded walk of
+ * cl2_set_connection_query(1) (whatever that setting is).  Per ray the stored triangle and its distance: (T, t_T) where the target is
+ * visible, the first blocker met and its t where it is not, (-1, +inf) where the ray misses T.  target < 0: the plain closest hit,
+ * as cl2_probe_traverse.  target >= the scene's triangle count: CL2_E_INVALID.  CL2_E_STATE when the scene has no 4-wide collapse
+ * or debug bit 13 is set. */
+int cl2_probe_visibility(cl2_renderer* r, const void* rays, size_t n_rays, const int32_t* target, int32_t* out_tri, float* out_t);
 
 /* -- denoiser: first-hit guide buffers and an edge-avoiding a-trous filter (csrc/denoise.hpp).  No reference counterpart:
  *    the reference's picture is the raw estimate (src/renderer.py:293-316).  Neither call touches the sample pipeline: the
