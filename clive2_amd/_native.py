@@ -97,6 +97,7 @@ EXPORTS = [
     "cl2_denoise_robust",
     "cl2_keep_picture", "cl2_kept_picture", "cl2_write_picture", "cl2_read_picture", "cl2_picture_log_sum", "cl2_picture_tone_map",
     "cl2_set_connection_query", "cl2_get_connection_query", "cl2_connection_query_active", "cl2_probe_visibility",
+    "cl2_set_strategy_mask", "cl2_get_strategy_mask",
 ]
 
 
@@ -161,6 +162,8 @@ def lib(variant=None):
         L.cl2_get_connection_query.argtypes = [C.c_void_p]
         L.cl2_connection_query_active.argtypes = [C.c_void_p]
         L.cl2_probe_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cl2_set_strategy_mask.argtypes = [C.c_void_p, C.c_uint64]
+        L.cl2_get_strategy_mask.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.cl2_set_export_stream.argtypes = [C.c_void_p, C.c_int]
         L.cl2_comm_info.argtypes = [C.c_void_p, C.POINTER(CommInfo)]
         L.cl2_tone_log_sum.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]

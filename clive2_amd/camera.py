@@ -61,12 +61,18 @@ class Camera:
 _LUMA_BGR = np.array([0.0722, 0.7152, 0.2126])
 
 
-def tone_map(image, exposure=2.0, white_point=1.0, verbose=False):
+def log_average(image):
+    """Lw = exp(mean log(0.1 + luma)) of a picture, float64: the scale `tone_map` divides by."""
+    luma = (image * _LUMA_BGR).sum(axis=2)
+    return np.exp(np.log(0.1 + luma).sum() / (image.shape[0] * image.shape[1]))
+
+
+def tone_map(image, exposure=2.0, white_point=1.0, verbose=False, Lw=None):
     """Log-average (Reinhard-style) operator -> uint8, BGR (`camera.py:73-82`): scale by
-    exposure / exp(mean log(0.1 + luma)), then compress x / (x + white^2)."""
+    exposure / exp(mean log(0.1 + luma)), then compress x / (x + white^2).  `Lw`: divide by this log-average instead of the
+    picture's own (pictures mapped with one Lw are comparable in brightness); None = the picture's own, as the reference."""
     if verbose:
         print(f"IN min: {np.min(image)}, mean: {np.mean(image)}, max: {np.max(image)}")
-    luma = (image * _LUMA_BGR).sum(axis=2)
-    log_avg = np.exp(np.log(0.1 + luma).sum() / (image.shape[0] * image.shape[1]))
+    log_avg = log_average(image) if Lw is None else Lw
     scaled = image * exposure / log_avg
     return (255 * scaled / (scaled + white_point ** 2)).astype(np.uint8)

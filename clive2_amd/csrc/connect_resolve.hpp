@@ -46,7 +46,11 @@ __device__ __forceinline__ V3 lds_v3(const float* base, int v) {
 // DET (cl2_set_reproducible): a t = 1 contribution is not added to the light image with float atomics but WRITTEN as a record
 // {target pixel, source slot} / {c.xyz, w} at slot (S-1) * B + pid -- the reference's own scatter `id + s * total_pixels`
 // (trace.metal:817-823) -- and summed per target pixel in a fixed order afterwards (det_splat.hpp).
-template <int S, bool DET>
+// STRAT (cl2_set_strategy_mask): `srow` holds the strategy bits of this t, bit S = pair (S, t).  A pair whose bit is clear is
+// evaluated exactly as before -- culls, verdict, MIS weight w, and w goes where it always goes -- but its COLOUR is left out: the
+// `total +=` statement is not executed, and the t = 1 splat or record carries (+0, +0, +0) with its w.  No reference counterpart
+// (trace.metal:649-825 sums all pairs).  STRAT = false is the kernel as it was: `srow` is not read.
+template <int S, bool DET, bool STRAT>
 __device__ __forceinline__ void resolve_pair(
         int t, int B, int pid, const LightVtx (&lv)[MAX_VERTS], const float (&GL)[MAX_VERTS], const float (&RL)[MAX_VERTS],
         unsigned l_spec, unsigned c_spec, bool spec7,
@@ -56,8 +60,10 @@ __device__ __forceinline__ void resolve_pair(
         unsigned long long mask, float2 h, const float4* __restrict__ tri_shade, const CamTris& cam_tris,
         const MaterialDev* __restrict__ mats, const CameraRec& cam, V3 focal, V3 cam_dir,
         V3& total, float& contrib_weight_sum, float4* __restrict__ light_image, float* splat_tab, int debug_flags,
-        unsigned* __restrict__ det_keys, float4* __restrict__ det_vals) {
+        unsigned* __restrict__ det_keys, float4* __restrict__ det_vals, [[maybe_unused]] unsigned srow) {
     const int tid = threadIdx.x;
+    bool keep = true;                                                         // this pair's colour is wanted
+    if constexpr (STRAT) keep = (srow >> S) & 1u;
     V3 c_o = c_o_in, c_n = c_n_in;
     float c_tot = c_tot_in, c_cos = c_cos_in;
     V3 dir_l_to_c = v3(0, 0, 0);
@@ -151,7 +157,7 @@ __device__ __forceinline__ void resolve_pair(
     if (S == 0) {                                                             // :783-786
         const V3 emission = v3(mats[c_meta & 0xFF].emission_alpha);
         const V3 color = prior_camera_color * emission;
-        total = total + ((w * 1.0f) * color) / p_s;
+        if (keep) total = total + ((w * 1.0f) * color) / p_s;
         contrib_weight_sum += w;
     } else if (t == 1) {                                                      // :787-793, :817-823, K8 :952-961
         const LightVtx& a = lv[S - 1];
@@ -167,7 +173,8 @@ __device__ __forceinline__ void resolve_pair(
 #endif
         const int frame_pixels = cam.pixel_width * cam.pixel_height;
         if (light_pixel_idx >= 0 && light_pixel_idx < frame_pixels && splat_on) {
-            const V3 c = ((w * shade) * prior_color) * mcol;
+            V3 c = ((w * shade) * prior_color) * mcol;
+            if constexpr (STRAT) { if (!keep) c = v3(0, 0, 0); }
             // the light image of THIS entry's sample stream (computed here, in the rare branch, not carried through the kernel:
             // it runs at 162 of 168 VGPRs)
             const int splat_idx = (pid - pid % frame_pixels) + light_pixel_idx;
@@ -212,20 +219,23 @@ __device__ __forceinline__ void resolve_pair(
             light_color = (prior_light_color * new_light_f) * v3(mats[a.meta & 0xFF].color_type);
         }
         const V3 color = camera_color * light_color;
-        total = total + ((w * Gj) * color) / p_s;
+        if (keep) total = total + ((w * Gj) * color) / p_s;
         contrib_weight_sum += w;
     }
 }
 
 // MAPPED (adaptive sampling, adaptive.hpp): the pixel of the filter weights is the slot map's map[pid] instead of pid % (W*H);
 // nothing else in the kernel takes an image pixel from a slot (the t = 1 splat takes only its plane base from it).
-template <int WAVES_PER_SIMD, bool MATS_LDS, bool DET = false, bool MAPPED = false>
+// STRAT: `strat` is the handle's strategy mask, bit (t - 1) * 7 + s for pair (s, t) (include/clive2_amd.h); launched only when the
+// mask is partial.  With STRAT = false the argument is not read.
+template <int WAVES_PER_SIMD, bool MATS_LDS, bool DET = false, bool MAPPED = false, bool STRAT = false>
 __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_connect_resolve(
         int B, PathBufs lp, PathBufs cp, const MaterialDev* __restrict__ mats_g, int n_mats,
         const float4* __restrict__ tri_shade, CamTris cam_tris, CameraRec cam, const unsigned long long* __restrict__ cmask,
         const float2* __restrict__ chit, float* __restrict__ agg, float4* __restrict__ light_image,
         float4* __restrict__ uni_out, Stats* stats, int debug_flags,
-        unsigned* __restrict__ det_keys, float4* __restrict__ det_vals, const int* __restrict__ map) {
+        unsigned* __restrict__ det_keys, float4* __restrict__ det_vals, const int* __restrict__ map,
+        [[maybe_unused]] unsigned long long strat) {
     __shared__ float GCs[(MAX_VERTS - 1) * BLOCK];     // GC[v] = G(camera[v], camera[v+1])
     __shared__ float RCs[(MAX_VERTS - 1) * BLOCK];     // RC[m]: ratio of camera vertex m with both neighbours on the camera side
     __shared__ float LNs[3 * MAX_VERTS * BLOCK];       // light vertex normals
@@ -356,11 +366,13 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_connect_resolve(
         if ((debug_flags & 2) && t >= 2) continue;      // timing dissection (test variant only): skip the t >= 2 / t == 1 pairs
         if ((debug_flags & 4) && t == 1) continue;
 #endif
+        unsigned srow = 0;
+        if constexpr (STRAT) srow = (unsigned)(strat >> ((t - 1) * 7)) & 0x7Fu;
 #define CL2_PAIR(S)                                                                                             \
         if ((S) <= Ll && t + (S) >= 2)                                                                          \
-            resolve_pair<S, DET>(t, B, pid, lv, GL, RL, l_spec, c_spec, spec7, c_o, c_n, cP0.w, cP1.w, cP3.w, c_cos, \
+            resolve_pair<S, DET, STRAT>(t, B, pid, lv, GL, RL, l_spec, c_spec, spec7, c_o, c_n, cP0.w, cP1.w, cP3.w, c_cos, \
                             c_tri, c_meta, prior_camera_color, GCs, RCs, LNs, LCs, mask, hits[S], tri_shade, cam_tris, mats, cam, \
-                            focal, cam_dir, total, contrib_weight_sum, light_image, splat_tab, debug_flags, det_keys, det_vals)
+                            focal, cam_dir, total, contrib_weight_sum, light_image, splat_tab, debug_flags, det_keys, det_vals, srow)
         CL2_PAIR(0); CL2_PAIR(1); CL2_PAIR(2); CL2_PAIR(3); CL2_PAIR(4); CL2_PAIR(5); CL2_PAIR(6);
 #undef CL2_PAIR
     }

@@ -111,6 +111,7 @@ struct cl2_renderer {
     int* d_ctag = nullptr;             // connection-ray queue: {slot, pixel} tags
     // reproducible light image (cl2_set_reproducible, det_splat.hpp): records of one pass, allocated on first use
     bool reproducible = false;
+    uint64_t strategy_mask = CL2_STRATEGY_ALL;   // cl2_set_strategy_mask: the (s, t) pairs whose colour is kept (connect_resolve.hpp STRAT)
     unsigned *d_det_keys = nullptr, *d_det_keys_sorted = nullptr, *d_det_slots = nullptr, *d_det_slots_sorted = nullptr;
     float4* d_det_vals = nullptr;
     void* d_det_tmp = nullptr;
@@ -695,10 +696,13 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
     const PathBufs& cp = set[CL2_CAMERA];
     {
         Timed t(r, ST_CONNECT_RESOLVE, st);
-#define CL2_RESOLVE_M(W, ML, DET, MAPPED)                                                                                        \
-        hipLaunchKernelGGL((k_connect_resolve<W, ML, DET, MAPPED>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, \
+#define CL2_RESOLVE_S(W, ML, DET, MAPPED, STRAT)                                                                                 \
+        hipLaunchKernelGGL((k_connect_resolve<W, ML, DET, MAPPED, STRAT>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, \
                            r->cam_tris, r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_agg, r->d_light_image, r->d_uni, r->d_stats, r->debug_flags, \
-                           r->d_det_keys, r->d_det_vals, map)
+                           r->d_det_keys, r->d_det_vals, map, (unsigned long long)r->strategy_mask)
+        // a full strategy mask (the default, or set explicitly) runs the kernels without the STRAT code
+#define CL2_RESOLVE_M(W, ML, DET, MAPPED) do { if (masked) CL2_RESOLVE_S(W, ML, DET, MAPPED, true); else CL2_RESOLVE_S(W, ML, DET, MAPPED, false); } while (0)
+        const bool masked = r->strategy_mask != CL2_STRATEGY_ALL;
 #define CL2_RESOLVE(W, ML, DET) do { if (map) CL2_RESOLVE_M(W, ML, DET, true); else CL2_RESOLVE_M(W, ML, DET, false); } while (0)
         // 3 waves per SIMD: what 165 VGPRs and 52 KB of LDS tables per workgroup allow (2 / 4 measured slower: DESIGN 6.1).  Debug
         // bits 4-6 = 7: one wave per camera vertex (tests/connect_resolve_wide.hpp: same results bit for bit, measured slower: 1.14 vs
@@ -709,6 +713,7 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
         // (it splats with atomics and writes no records: the sort + gather below would read buffers it never filled)
         if (occ == 7 && r->reproducible) return fail(r, CL2_E_INVALID, "the cross-check resolve kernel has no reproducible form: clear debug bits 4-6 or cl2_set_reproducible(0)");
         if (occ == 7 && r->density) return fail(r, CL2_E_STATE, "the cross-check resolve kernel has no mapped form: cl2_set_sample_density(NULL) or clear debug bits 4-6");
+        if (occ == 7 && masked) return fail(r, CL2_E_INVALID, "the cross-check resolve kernel has no masked form: clear debug bits 4-6 or set the full strategy mask");
 #ifdef CL2_TEST_VARIANT
         if (occ == 7)
             hipLaunchKernelGGL(k_connect_resolve_wide, dim3((B + RW_PIX - 1) / RW_PIX), dim3(RW_BLOCK), 0, st, B, lp, cp, r->d_mats,
@@ -731,6 +736,7 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
         }
 #undef CL2_RESOLVE
 #undef CL2_RESOLVE_M
+#undef CL2_RESOLVE_S
     }
     HIP_TRY(r, hipGetLastError());
     if (r->reproducible) {
@@ -1788,6 +1794,8 @@ int cl2_set_debug_flags(cl2_renderer* r, int flags) {
     if (((flags >> 4) & 7) != 0 && ((flags >> 4) & 7) != 7) return fail(r, CL2_E_INVALID, "debug bits 4-6 must be 0 or 7");
     if ((flags & (3 << 13)) && r->connection_query == 1)
         return fail(r, CL2_E_INVALID, "debug bits 13 and 14 are A/B switches of the closest-hit walk; the seeded connection query has no such form: cl2_set_connection_query(0) first");
+    if (((flags >> 4) & 7) == 7 && r->strategy_mask != CL2_STRATEGY_ALL)
+        return fail(r, CL2_E_INVALID, "the cross-check resolve kernel (debug bits 4-6 = 7) has no masked form: set the full strategy mask first");
     r->debug_flags = flags;
     r->bvh.n_fast_nodes = ((flags >> 7) & 1) ? 0 : r->n_fast;      // bit 7: walk the full table (A/B of the pruned one)
     r->bvh.fast_flat = flat_walk(r);     // bit 11: per-lane walk of a flat pruned table (A/B of the wave-uniform one); bit 26: its clamped loop
@@ -1806,6 +1814,23 @@ int cl2_set_reproducible(cl2_renderer* r, int on) {
     return CL2_OK;
 }
 int cl2_get_reproducible(const cl2_renderer* r) { return r ? (r->reproducible ? 1 : 0) : CL2_E_INVALID; }
+/* Strategy mask (include/clive2_amd.h): bit (t - 1) * 7 + s keeps the colour of pair (s, t); every w is kept whatever the mask.  Only
+ * launch_resolve reads it: a full mask launches the default kernels, a partial one the STRAT instantiations. */
+int cl2_set_strategy_mask(cl2_renderer* r, uint64_t mask) {
+    if (!r) return CL2_E_INVALID;
+    mask &= CL2_STRATEGY_ALL;
+    if (mask != CL2_STRATEGY_ALL && ((r->debug_flags >> 4) & 7) == 7)
+        return fail(r, CL2_E_INVALID, "the cross-check resolve kernel (debug bits 4-6 = 7) has no masked form: clear debug bits 4-6 first");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    r->strategy_mask = mask;
+    return CL2_OK;
+}
+int cl2_get_strategy_mask(const cl2_renderer* r, uint64_t* mask_out) {
+    if (!r || !mask_out) return CL2_E_INVALID;
+    *mask_out = r->strategy_mask;
+    return CL2_OK;
+}
 
 int cl2_set_subpath_gather(cl2_renderer* r, int lanes, int wait_steps) {
     if (!r) return CL2_E_INVALID;

@@ -7,6 +7,8 @@ instead of opening a cv2 window (display code is out of scope).
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --denoise --variance-guided --out cornell_guided.png
     python -m clive2_amd.render --scene empty --samples 256 --robust --out cornell_robust.png
     python -m clive2_amd.render --scene empty --samples 256 --robust-denoise --out cornell_robust_denoised.png
+    python -m clive2_amd.render --scene empty --samples 64 --path-length 3: --out cornell_indirect_only.png
+    python -m clive2_amd.render --scene empty --samples 64 --layers cornell
 
 Several GPUs: start one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE in the environment (e.g.
 `python -m torch.distributed.run --nproc-per-node N -m clive2_amd.render ...`; any spawner will do, torch
@@ -18,10 +20,37 @@ import time
 
 import numpy as np
 
-from . import _native
+from . import _native, strategies
+from .camera import log_average, tone_map
 from .distributed import rank_info, samples_for_rank, join_communicator
 from .renderer import ERROR_FLOOR, UNIFORM_SHARE, Renderer, RendererError, stream_seeds
 from .scene import create_scene_from_preset
+
+
+def _save(path, image):
+    try:
+        from PIL import Image
+        Image.fromarray(np.ascontiguousarray(image[:, :, ::-1])).save(path)
+    except ImportError:
+        np.save(path + ".npy", image)
+
+
+def _write_layers(renderer, args, K):
+    """--layers: the three layer pictures, tone-mapped with the log-average of their SUM so that their brightness is comparable."""
+    t0 = time.time()
+    try:
+        layers = renderer.render_layers(-(-args.samples // K))
+    finally:
+        renderer.close()
+    print(f"[rank 0] rendering {len(layers)} layers took {time.time() - t0:.2f} seconds")
+    total = None
+    for pic in layers.values():
+        total = pic.copy() if total is None else total + pic
+    Lw = log_average(total)
+    for name, pic in layers.items():
+        _save(f"{args.layers}_{name}.png", tone_map(pic, exposure=4.0, Lw=Lw))
+    np.savez(f"{args.layers}_layers.npz", **layers)
+    return 0
 
 
 def main(argv=None):
@@ -76,6 +105,17 @@ def main(argv=None):
                          "kept (Renderer.robust_guided_image, DESIGN.md 6.8): M buckets per pixel, 3..16, default 8; the feature pass "
                          "takes --feature-samples; tone-mapped on the host unless --device-tonemap.  Goes with --target-error and --adaptive (the error "
                          "metric stays on the plain estimates), not with --robust, --denoise or --variance-guided")
+    ap.add_argument("--strategies", type=str, default=None, metavar="S,T;S,T;...",
+                    help="keep the colour of these (s, t) connection strategies only (s light vertices 0..6, t camera vertices "
+                         "1..6, s + t >= 2; Renderer.set_strategy_mask, DESIGN.md 6.11): every strategy keeps its MIS weight, so the "
+                         "pictures of a partition add up to the full one")
+    ap.add_argument("--path-length", type=str, default=None, metavar="A[:B]",
+                    help="keep the strategies whose paths have exactly A edges (A), A to B edges (A:B) or A and more (A:); "
+                         "1 = emitters seen directly, 2 = direct light.  Not with --strategies")
+    ap.add_argument("--layers", type=str, default=None, metavar="PREFIX",
+                    help="render the emission / direct / indirect layers (Renderer.render_layers, one render of --samples each from "
+                         "the same seeds) and write PREFIX_emission.png, PREFIX_direct.png, PREFIX_indirect.png, tone-mapped with "
+                         "the log-average of their sum, and PREFIX_layers.npz with the float pictures (one rank only)")
     args = ap.parse_args(argv)
     # refused before any renderer is made
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
@@ -99,7 +139,31 @@ def main(argv=None):
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
 
+    if args.strategies is not None and args.path_length is not None:
+        ap.error("--strategies and --path-length both set the strategy mask: give one")
+    strategy_mask = None
+    try:
+        if args.strategies is not None:
+            strategy_mask = strategies.parse_strategies(args.strategies)
+        if args.path_length is not None:
+            strategy_mask = strategies.parse_path_length(args.path_length)
+    except ValueError as e:
+        ap.error(str(e))
+    if args.layers is not None:
+        if strategy_mask is not None:
+            ap.error("--layers sets the strategy mask of each layer itself: it does not go with --strategies or --path-length")
+        if args.target_error is not None:
+            ap.error("--layers renders --samples per layer: it does not go with --target-error")
+        if args.denoise or args.variance_guided or args.robust or args.robust_denoise:
+            ap.error("--layers writes the plain layer pictures: it does not go with --denoise, --variance-guided, --robust or --robust-denoise")
+        if args.device_tonemap:
+            ap.error("--layers tone-maps its pictures on the host with one log-average: it does not go with --device-tonemap")
+        if not args.layers:
+            ap.error("--layers needs a file name prefix")
+
     rank, local_rank, world = rank_info()
+    if args.layers is not None and world > 1:
+        ap.error("--layers renders on one GPU: run it with a single rank (WORLD_SIZE=1)")
     if args.target_error is not None and world > 1:
         ap.error("--target-error renders one frame on one GPU: run it with a single rank (WORLD_SIZE=1)")
     scene = create_scene_from_preset(args.scene, pixel_width=args.width, pixel_height=args.height)
@@ -118,8 +182,12 @@ def main(argv=None):
         renderer.set_error_tracking(True)
     if args.robust or args.robust_denoise:
         renderer.set_robust_buckets(args.robust or args.robust_denoise)
+    if strategy_mask is not None:
+        renderer.set_strategy_mask(strategy_mask)      # before the first sample, the same on every rank
     # seed buffers of the job: stream k of rank r is buffer r * K + k
     renderer.set_seeds(stream_seeds(args.width * args.height, K, first_rank=rank * K))
+    if args.layers is not None:
+        return _write_layers(renderer, args, K)
     if world > 1:
         join_communicator(renderer, rank, world)
     t0 = time.time()

@@ -22,6 +22,7 @@ import numpy as np
 from . import _native
 from ._native import RendererError, Counters, Organisation, ptr
 from . import struct_types as st
+from . import strategies
 from .camera import tone_map
 from .constants import timed, MAX_PATH_LENGTH  # noqa: F401
 
@@ -487,6 +488,43 @@ class Renderer:
         float atomics -- two renders of the same scene and seeds then agree byte for byte, as the reference's sort + gather
         chain does (renderer.py:97-111, :213-250).  Off by default (costs a radix sort per pass)."""
         self._check(self._L.cl2_set_reproducible(self._h, int(bool(on))), "set_reproducible")
+
+    # ---- strategy mask (cl2_set_strategy_mask, clive2_amd/strategies.py, DESIGN.md 6.11) ----
+    def set_strategy_mask(self, mask_or_pairs=None):
+        """Keep the colour of these (s, t) strategy pairs only: a 64-bit mask (strategies.bit / mask / path_length / LAYERS ...) or
+        an iterable of (s, t) pairs; None = all 41 (the default).  A masked pair is still evaluated and keeps its MIS weight
+        wherever that goes today, so the `radiance` of masks that partition strategies.ALL add up to the full picture; seeds,
+        paths, filter weights, the unidirectional picture and the ray counters are those of the unmasked render.  Bits outside the 41
+        are dropped.  The mask stays until it is set again (uploads, stream changes and resets keep it)."""
+        m = strategies.to_mask(mask_or_pairs)
+        self._check(self._L.cl2_set_strategy_mask(self._h, C.c_uint64(m)), "cl2_set_strategy_mask")
+
+    def strategy_mask(self):
+        m = C.c_uint64(0)
+        self._check(self._L.cl2_get_strategy_mask(self._h, C.byref(m)), "cl2_get_strategy_mask")
+        return int(m.value)
+
+    def render_layers(self, passes, layers=strategies.LAYERS, seeds=None):
+        """One render per layer of `layers` ({name: mask or pairs}; default emission / direct / indirect), all from the same seeds
+        and therefore along the same paths: per layer reset_accumulators(), set_seeds(seeds), set_strategy_mask(layer),
+        run_samples(passes), `radiance`.  Returns {name: (H, W, 3) float32, BGR}; layers that partition strategies.ALL add up to
+        the unmasked `radiance` of the same seeds, to float rounding (use set_reproducible(True) for a light image summed in one
+        order).  `seeds`: as set_seeds; None = the handle's current seeds.  The mask found on entry is restored; the accumulators
+        are left holding the last layer.  With layers=strategies.SINGLETONS this is the per-strategy pyramid."""
+        start = self.get_random_buffer() if seeds is None else np.array(seeds, dtype=np.uint32, copy=True)
+        masks = {name: strategies.to_mask(m) for name, m in dict(layers).items()}     # refused before anything is rendered
+        found = self.strategy_mask()
+        out = {}
+        try:
+            for name, m in masks.items():
+                self.reset_accumulators()
+                self.set_seeds(start)
+                self.set_strategy_mask(m)
+                self.run_samples(passes)
+                out[name] = self.radiance
+        finally:
+            self.set_strategy_mask(found)
+        return out
 
     def set_subpath_gather(self, lanes=0, wait_steps=0):
         """Whole-subpath launch: lanes gathered / steps waited before a wave runs its bounce phase (0 = default)."""

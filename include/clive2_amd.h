@@ -616,6 +616,32 @@ int cl2_picture_log_sum(cl2_renderer* r, double* sum_out);
 int cl2_picture_tone_map(cl2_renderer* r, double exposure, double white_point, double log_average /* Lw */, uint8_t* out_bgr,
                          size_t n_bytes);
 
+/* ---- strategy mask: render any subset of the (s, t) connection strategies (csrc/connect_resolve.hpp STRAT) ----
+ * A pixel-sample is a sum over the strategy pairs (s, t): s = light vertices used (0..6), t = camera vertices used (1..6),
+ * s + t >= 2.  Pair (s, t) owns bit (t - 1) * 7 + s of a 64-bit mask: 41 valid bits (CL2_STRATEGY_ALL); the other 23 are dropped on
+ * set and read back as 0.  The default is all 41 set.
+ * While a pair's bit is clear, everything the reference computes for the pair is still computed -- the culls, the connection ray, the
+ * visibility verdict, the MIS weight w -- and w still goes where it goes today: aggregator row 12 (contrib_weight_sum) for t >= 2,
+ * the .w of the light-image splat or record for t = 1.  Only the COLOUR is left out: for t >= 2 the pair is not added to
+ * total_contribution; for t = 1 the splat or record carries colour (+0, +0, +0) with its w.  The picture is the ratio sum x / sum w,
+ * so keeping every w makes masked pictures a decomposition: for masks that partition the 41 pairs the pictures add up to the full
+ * one, to float rounding.
+ * NOT touched: the filter weights (aggregator rows 0..8), row 12, the light weight, the unidirectional estimate, the seeds and the
+ * random numbers drawn (renders from the same seeds walk the same paths whatever the mask), the ray counters -- no connection ray is
+ * skipped, a masked pair's w needs its verdict.  Moments, robust buckets, the sample density and the denoisers see the masked
+ * addends (x masked, w full) and describe the masked picture.
+ * A full mask runs the default kernels (byte-identical to a handle that never set one); a partial one runs the masked instantiations
+ * of k_connect_resolve, at the occupancy of their default counterparts (no scratch).  The mask survives cl2_upload_scene, cl2_set_sample_streams and
+ * cl2_reset_accumulators and applies to cl2_join_paths and to cl2_run_samples / cl2_tune / cl2_run_until alike.  A partial mask is
+ * refused together with debug bits 4-6 = 7, whichever is set second (CL2_E_INVALID, the earlier setting is kept): the test variant's
+ * cross-check resolve kernel has no masked form.  In a multi-rank job every rank must set the same mask: that is the caller's
+ * business and is not checked.  NULL handle or NULL mask_out: CL2_E_INVALID.
+ * No reference counterpart (src/trace.metal:649-825 sums all pairs). */
+#define CL2_STRATEGY_BIT(s, t)  ((uint64_t)1 << (((t) - 1) * 7 + (s)))
+#define CL2_STRATEGY_ALL        ((uint64_t)0x3FFFFFFFFFE)   /* the 41 valid bits: bits 1..41, (0, 1) is not a pair */
+int cl2_set_strategy_mask(cl2_renderer* r, uint64_t mask);
+int cl2_get_strategy_mask(const cl2_renderer* r, uint64_t* mask_out);
+
 #ifdef __cplusplus
 }
 #endif

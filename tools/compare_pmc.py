@@ -16,7 +16,10 @@ RENAMED = {"k_finalize_accumulate": "k_finalize_accumulate<false>", "k_accumulat
            "k_finalize_accumulate<false>": "k_finalize_accumulate<false,false>", "k_accumulate<false>": "k_accumulate<false,false>",
            "k_gen_rays": "k_gen_rays<false>", "k_gen_camera_rays": "k_gen_camera_rays<false>",
            **{f"k_connect_resolve<{a}>": f"k_connect_resolve<{a},false>"
-              for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true")}}
+              for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true")},
+           # r19: the resolve kernel gained a STRAT parameter (strategy mask); the render runs <..., false>
+           **{f"k_connect_resolve<{a},{m}>": f"k_connect_resolve<{a},{m},false>"
+              for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true") for m in ("false", "true")}}
 
 
 def kernels(tag, workload):
