@@ -42,6 +42,34 @@ __device__ __forceinline__ V3 lds_v3(const float* base, int v) {
     return v3(base[(3 * v + 0) * BLOCK + threadIdx.x], base[(3 * v + 1) * BLOCK + threadIdx.x], base[(3 * v + 2) * BLOCK + threadIdx.x]);
 }
 
+// Layer accumulators (cl2_set_layers, layers.hpp): the handle's table as the resolve kernel takes it, by value.  Pair (s, t) has a
+// 4-bit code at bits 4 s .. 4 s + 3 of the 32-bit row of t: 0 = in no layer, l + 1 = in layer l.  Rows t = 1, 2 are the halves of
+// w[0], rows 3, 4 of w[1], rows 5, 6 of w[2] -- chosen with selects, so the argument is only ever indexed by constants.
+constexpr int LAYERS_MAX = 8;              // CL2_MAX_LAYERS (include/clive2_amd.h)
+struct LayerCodes {
+    unsigned long long w[3];
+    int n_layers;
+};
+__device__ __forceinline__ unsigned layer_row(const LayerCodes& lc, int t) {
+    const unsigned long long w = (t <= 2) ? lc.w[0] : ((t <= 4) ? lc.w[1] : lc.w[2]);
+    return (unsigned)(w >> (((t - 1) & 1) * 32));
+}
+// `code` is the same in every lane of the wave (S is a template parameter and the lanes run the t loop in lockstep): a scalar
+// switch picks the registers, there is no register array indexed by a lane value.
+__device__ __forceinline__ void layer_add(V3 (&lt)[LAYERS_MAX], unsigned code, const V3& term) {
+    switch (code) {
+        case 1: lt[0] = lt[0] + term; break;
+        case 2: lt[1] = lt[1] + term; break;
+        case 3: lt[2] = lt[2] + term; break;
+        case 4: lt[3] = lt[3] + term; break;
+        case 5: lt[4] = lt[4] + term; break;
+        case 6: lt[5] = lt[5] + term; break;
+        case 7: lt[6] = lt[6] + term; break;
+        case 8: lt[7] = lt[7] + term; break;
+        default: break;
+    }
+}
+
 // One strategy pair with s = S (compile time).  Returns true when a contribution was produced.
 // DET (cl2_set_reproducible): a t = 1 contribution is not added to the light image with float atomics but WRITTEN as a record
 // {target pixel, source slot} / {c.xyz, w} at slot (S-1) * B + pid -- the reference's own scatter `id + s * total_pixels`
@@ -50,7 +78,12 @@ __device__ __forceinline__ V3 lds_v3(const float* base, int v) {
 // evaluated exactly as before -- culls, verdict, MIS weight w, and w goes where it always goes -- but its COLOUR is left out: the
 // `total +=` statement is not executed, and the t = 1 splat or record carries (+0, +0, +0) with its w.  No reference counterpart
 // (trace.metal:649-825 sums all pairs).  STRAT = false is the kernel as it was: `srow` is not read.
-template <int S, bool DET, bool STRAT>
+// LAYERS (cl2_set_layers): everything is computed as with STRAT = false; in addition the colour term of a t >= 2 or s = 0 pair --
+// the very value added to `total`, computed once -- is added to the running total `ltot` of the pair's layer (code `lrow >> 4 S`),
+// in the kernel's pair order, which is the sequence of additions the masked kernel performs for that layer's mask; a t = 1 pair
+// with atomics also adds its colour to lay_light[layer][entry] (the records of DET need nothing: a record's slot names its pair).
+// LAYERS = false: `lrow`, `ltot` and `lay_light` are not read.
+template <int S, bool DET, bool STRAT, bool LAYERS = false>
 __device__ __forceinline__ void resolve_pair(
         int t, int B, int pid, const LightVtx (&lv)[MAX_VERTS], const float (&GL)[MAX_VERTS], const float (&RL)[MAX_VERTS],
         unsigned l_spec, unsigned c_spec, bool spec7,
@@ -60,8 +93,10 @@ __device__ __forceinline__ void resolve_pair(
         unsigned long long mask, float2 h, const float4* __restrict__ tri_shade, const CamTris& cam_tris,
         const MaterialDev* __restrict__ mats, const CameraRec& cam, V3 focal, V3 cam_dir,
         V3& total, float& contrib_weight_sum, float4* __restrict__ light_image, float* splat_tab, int debug_flags,
-        unsigned* __restrict__ det_keys, float4* __restrict__ det_vals, [[maybe_unused]] unsigned srow) {
+        unsigned* __restrict__ det_keys, float4* __restrict__ det_vals, [[maybe_unused]] unsigned srow,
+        [[maybe_unused]] unsigned lrow, [[maybe_unused]] V3 (&ltot)[LAYERS_MAX], [[maybe_unused]] float4* __restrict__ lay_light) {
     const int tid = threadIdx.x;
+    [[maybe_unused]] const unsigned lcode = LAYERS ? ((lrow >> (4 * S)) & 15u) : 0u;     // wave-uniform
     bool keep = true;                                                         // this pair's colour is wanted
     if constexpr (STRAT) keep = (srow >> S) & 1u;
     V3 c_o = c_o_in, c_n = c_n_in;
@@ -157,7 +192,11 @@ __device__ __forceinline__ void resolve_pair(
     if (S == 0) {                                                             // :783-786
         const V3 emission = v3(mats[c_meta & 0xFF].emission_alpha);
         const V3 color = prior_camera_color * emission;
-        if (keep) total = total + ((w * 1.0f) * color) / p_s;
+        if constexpr (LAYERS) {
+            const V3 term = ((w * 1.0f) * color) / p_s;
+            total = total + term;
+            layer_add(ltot, lcode, term);
+        } else if (keep) total = total + ((w * 1.0f) * color) / p_s;
         contrib_weight_sum += w;
     } else if (t == 1) {                                                      // :787-793, :817-823, K8 :952-961
         const LightVtx& a = lv[S - 1];
@@ -202,6 +241,12 @@ __device__ __forceinline__ void resolve_pair(
                 const int pix = __float_as_int(tab[slot]);
                 const float val = tab[(1 + comp) * 64 + slot];
                 atomicAdd(reinterpret_cast<float*>(&light_image[pix]) + comp, val);
+                if constexpr (LAYERS) {
+                    // the same exchange, so consecutive lanes still cover one pixel's components; the layer is the same in
+                    // every lane of this branch.  pix < B (splat_idx above) and lcode - 1 < n_layers (the host's table).
+                    if (lcode != 0u && comp < 3)
+                        atomicAdd(reinterpret_cast<float*>(&lay_light[(size_t)(lcode - 1u) * B + pix]) + comp, val);
+                }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -219,7 +264,11 @@ __device__ __forceinline__ void resolve_pair(
             light_color = (prior_light_color * new_light_f) * v3(mats[a.meta & 0xFF].color_type);
         }
         const V3 color = camera_color * light_color;
-        if (keep) total = total + ((w * Gj) * color) / p_s;
+        if constexpr (LAYERS) {
+            const V3 term = ((w * Gj) * color) / p_s;
+            total = total + term;
+            layer_add(ltot, lcode, term);
+        } else if (keep) total = total + ((w * Gj) * color) / p_s;
         contrib_weight_sum += w;
     }
 }
@@ -228,14 +277,20 @@ __device__ __forceinline__ void resolve_pair(
 // nothing else in the kernel takes an image pixel from a slot (the t = 1 splat takes only its plane base from it).
 // STRAT: `strat` is the handle's strategy mask, bit (t - 1) * 7 + s for pair (s, t) (include/clive2_amd.h); launched only when the
 // mask is partial.  With STRAT = false the argument is not read.
-template <int WAVES_PER_SIMD, bool MATS_LDS, bool DET = false, bool MAPPED = false, bool STRAT = false>
+// LAYERS: `lcodes` is the handle's layer table; the layer totals go to lay_agg[l][3][B] (the stride of the aggregator rows) for
+// l < lcodes.n_layers, everything else is written as with STRAT = false.  Launched only while a table is set, only with
+// MAPPED = false and STRAT = false, at two waves per SIMD: the 24 layer totals are registers (3 waves leave 168, the kernel
+// alone takes 163).  With LAYERS = false the three arguments are not read.
+template <int WAVES_PER_SIMD, bool MATS_LDS, bool DET = false, bool MAPPED = false, bool STRAT = false, bool LAYERS = false>
 __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_connect_resolve(
         int B, PathBufs lp, PathBufs cp, const MaterialDev* __restrict__ mats_g, int n_mats,
         const float4* __restrict__ tri_shade, CamTris cam_tris, CameraRec cam, const unsigned long long* __restrict__ cmask,
         const float2* __restrict__ chit, float* __restrict__ agg, float4* __restrict__ light_image,
         float4* __restrict__ uni_out, Stats* stats, int debug_flags,
         unsigned* __restrict__ det_keys, float4* __restrict__ det_vals, const int* __restrict__ map,
-        [[maybe_unused]] unsigned long long strat) {
+        [[maybe_unused]] unsigned long long strat, [[maybe_unused]] LayerCodes lcodes, [[maybe_unused]] float* __restrict__ lay_agg,
+        [[maybe_unused]] float4* __restrict__ lay_light) {
+    static_assert(!LAYERS || (!MAPPED && !STRAT), "layer accumulators: no mapped and no masked form");
     __shared__ float GCs[(MAX_VERTS - 1) * BLOCK];     // GC[v] = G(camera[v], camera[v+1])
     __shared__ float RCs[(MAX_VERTS - 1) * BLOCK];     // RC[m]: ratio of camera vertex m with both neighbours on the camera side
     __shared__ float LNs[3 * MAX_VERTS * BLOCK];       // light vertex normals
@@ -334,6 +389,11 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_connect_resolve(
 
     V3 total = v3(0, 0, 0);
     float contrib_weight_sum = 0.0f;
+    V3 ltot[LAYERS_MAX];                             // LAYERS: the layers' running totals (dead code otherwise)
+    if constexpr (LAYERS) {
+#pragma unroll
+        for (int l = 0; l < LAYERS_MAX; l++) ltot[l] = v3(0, 0, 0);
+    }
     float4 uni = make_float4(0, 0, 0, 0);
 
     V3 prior_camera_color = v3(0, 0, 0);            // rays[t-2].color: the previous iteration's P3 (read once, not again)
@@ -368,11 +428,14 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_connect_resolve(
 #endif
         unsigned srow = 0;
         if constexpr (STRAT) srow = (unsigned)(strat >> ((t - 1) * 7)) & 0x7Fu;
+        unsigned lrow = 0;
+        if constexpr (LAYERS) lrow = layer_row(lcodes, t);
 #define CL2_PAIR(S)                                                                                             \
         if ((S) <= Ll && t + (S) >= 2)                                                                          \
-            resolve_pair<S, DET, STRAT>(t, B, pid, lv, GL, RL, l_spec, c_spec, spec7, c_o, c_n, cP0.w, cP1.w, cP3.w, c_cos, \
+            resolve_pair<S, DET, STRAT, LAYERS>(t, B, pid, lv, GL, RL, l_spec, c_spec, spec7, c_o, c_n, cP0.w, cP1.w, cP3.w, c_cos, \
                             c_tri, c_meta, prior_camera_color, GCs, RCs, LNs, LCs, mask, hits[S], tri_shade, cam_tris, mats, cam, \
-                            focal, cam_dir, total, contrib_weight_sum, light_image, splat_tab, debug_flags, det_keys, det_vals, srow)
+                            focal, cam_dir, total, contrib_weight_sum, light_image, splat_tab, debug_flags, det_keys, det_vals, srow, \
+                            lrow, ltot, lay_light)
         CL2_PAIR(0); CL2_PAIR(1); CL2_PAIR(2); CL2_PAIR(3); CL2_PAIR(4); CL2_PAIR(5); CL2_PAIR(6);
 #undef CL2_PAIR
     }
@@ -411,6 +474,16 @@ __global__ __launch_bounds__(BLOCK, WAVES_PER_SIMD) void k_connect_resolve(
     agg[(size_t)10 * B + pid] = total.y;
     agg[(size_t)11 * B + pid] = total.z;
     agg[(size_t)12 * B + pid] = contrib_weight_sum;
+    if constexpr (LAYERS) {
+#pragma unroll
+        for (int l = 0; l < LAYERS_MAX; l++) {
+            if (l < lcodes.n_layers) {
+                lay_agg[(size_t)(3 * l + 0) * B + pid] = ltot[l].x;
+                lay_agg[(size_t)(3 * l + 1) * B + pid] = ltot[l].y;
+                lay_agg[(size_t)(3 * l + 2) * B + pid] = ltot[l].z;
+            }
+        }
+    }
 
     uni_out[pid] = uni;
 }

@@ -26,6 +26,7 @@
 #include "denoise_robust.hpp"
 #include "error_estimate.hpp"
 #include "adaptive.hpp"
+#include "layers.hpp"
 #include "tonemap.hpp"
 #include "tonemap_picture.hpp"
 #include "det_splat.hpp"
@@ -112,6 +113,14 @@ struct cl2_renderer {
     // reproducible light image (cl2_set_reproducible, det_splat.hpp): records of one pass, allocated on first use
     bool reproducible = false;
     uint64_t strategy_mask = CL2_STRATEGY_ALL;   // cl2_set_strategy_mask: the (s, t) pairs whose colour is kept (connect_resolve.hpp STRAT)
+    // layer accumulators (cl2_set_layers, layers.hpp): the table, its per-entry buffers [L][3][B] / [L][B] and the sums [L][3][W*H]
+    int n_layers = 0;                    // 0 = off (the default)
+    uint64_t layer_masks[CL2_MAX_LAYERS] = {};
+    LayerCodes lcodes{};                 // the table as the resolve kernel takes it
+    float* d_lay_agg = nullptr;
+    float4* d_lay_light = nullptr;
+    float* d_lacc = nullptr;
+    bool lay_valid = false;              // every sample in the accumulators was rendered under this table (the rules of mom_valid)
     unsigned *d_det_keys = nullptr, *d_det_keys_sorted = nullptr, *d_det_slots = nullptr, *d_det_slots_sorted = nullptr;
     float4* d_det_vals = nullptr;
     void* d_det_tmp = nullptr;
@@ -690,6 +699,17 @@ int ensure_det_buffers(cl2_renderer* r) {
     return CL2_OK;
 }
 
+inline unsigned layer_row_host(const LayerCodes& lc, int t) { return (unsigned)(lc.w[(t - 1) >> 1] >> (((t - 1) & 1) * 32)); }
+
+// the layers' share of launch_accumulate / launch_finalize_accumulate (layers.hpp): same stream, right beside the main kernel
+int launch_layers_accumulate(cl2_renderer* r, hipStream_t st) {
+    if (r->n_layers == 0) return CL2_OK;
+    hipLaunchKernelGGL(k_layers_accumulate, dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, r->B, r->W, r->H, r->n_layers,
+                       (const float*)r->d_agg, (const float*)r->d_lay_agg, r->d_lay_light, r->d_lacc);
+    HIP_TRY(r, hipGetLastError());
+    return CL2_OK;
+}
+
 int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs, const int* map = nullptr) {
     const int B = r->B;
     const PathBufs& lp = set[CL2_LIGHT];
@@ -699,11 +719,17 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
 #define CL2_RESOLVE_S(W, ML, DET, MAPPED, STRAT)                                                                                 \
         hipLaunchKernelGGL((k_connect_resolve<W, ML, DET, MAPPED, STRAT>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, \
                            r->cam_tris, r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_agg, r->d_light_image, r->d_uni, r->d_stats, r->debug_flags, \
-                           r->d_det_keys, r->d_det_vals, map, (unsigned long long)r->strategy_mask)
+                           r->d_det_keys, r->d_det_vals, map, (unsigned long long)r->strategy_mask, r->lcodes, r->d_lay_agg, r->d_lay_light)
+        // a layer table (cl2_set_layers): the LAYERS instantiations, two waves per SIMD (their 24 layer totals are registers)
+#define CL2_RESOLVE_L(ML, DET)                                                                                                   \
+        hipLaunchKernelGGL((k_connect_resolve<2, ML, DET, false, false, true>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, \
+                           r->cam_tris, r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_agg, r->d_light_image, r->d_uni, r->d_stats, r->debug_flags, \
+                           r->d_det_keys, r->d_det_vals, (const int*)nullptr, (unsigned long long)r->strategy_mask, r->lcodes, r->d_lay_agg, r->d_lay_light)
         // a full strategy mask (the default, or set explicitly) runs the kernels without the STRAT code
 #define CL2_RESOLVE_M(W, ML, DET, MAPPED) do { if (masked) CL2_RESOLVE_S(W, ML, DET, MAPPED, true); else CL2_RESOLVE_S(W, ML, DET, MAPPED, false); } while (0)
         const bool masked = r->strategy_mask != CL2_STRATEGY_ALL;
-#define CL2_RESOLVE(W, ML, DET) do { if (map) CL2_RESOLVE_M(W, ML, DET, true); else CL2_RESOLVE_M(W, ML, DET, false); } while (0)
+#define CL2_RESOLVE(W, ML, DET) do { if (layered) CL2_RESOLVE_L(ML, DET); else if (map) CL2_RESOLVE_M(W, ML, DET, true); else CL2_RESOLVE_M(W, ML, DET, false); } while (0)
+        const bool layered = r->n_layers > 0;
         // 3 waves per SIMD: what 165 VGPRs and 52 KB of LDS tables per workgroup allow (2 / 4 measured slower: DESIGN 6.1).  Debug
         // bits 4-6 = 7: one wave per camera vertex (tests/connect_resolve_wide.hpp: same results bit for bit, measured slower: 1.14 vs
         // 0.93 ms; a second implementation kept as a cross-check, built only with -DCL2_TEST_VARIANT = libclive2_amd_test.so)
@@ -714,6 +740,10 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
         if (occ == 7 && r->reproducible) return fail(r, CL2_E_INVALID, "the cross-check resolve kernel has no reproducible form: clear debug bits 4-6 or cl2_set_reproducible(0)");
         if (occ == 7 && r->density) return fail(r, CL2_E_STATE, "the cross-check resolve kernel has no mapped form: cl2_set_sample_density(NULL) or clear debug bits 4-6");
         if (occ == 7 && masked) return fail(r, CL2_E_INVALID, "the cross-check resolve kernel has no masked form: clear debug bits 4-6 or set the full strategy mask");
+        // (the setters refuse these combinations; a pass must never run the layered kernels on them)
+        if (layered && occ == 7) return fail(r, CL2_E_INVALID, "the cross-check resolve kernel has no layered form: clear debug bits 4-6 or cl2_set_layers(NULL, 0)");
+        if (layered && masked) return fail(r, CL2_E_STATE, "layer accumulators need the full strategy mask: cl2_set_strategy_mask(CL2_STRATEGY_ALL) or cl2_set_layers(NULL, 0)");
+        if (layered && map) return fail(r, CL2_E_STATE, "layer accumulators have no mapped form: cl2_set_sample_density(NULL) or cl2_set_layers(NULL, 0)");
 #ifdef CL2_TEST_VARIANT
         if (occ == 7)
             hipLaunchKernelGGL(k_connect_resolve_wide, dim3((B + RW_PIX - 1) / RW_PIX), dim3(RW_BLOCK), 0, st, B, lp, cp, r->d_mats,
@@ -736,6 +766,7 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
         }
 #undef CL2_RESOLVE
 #undef CL2_RESOLVE_M
+#undef CL2_RESOLVE_L
 #undef CL2_RESOLVE_S
     }
     HIP_TRY(r, hipGetLastError());
@@ -747,8 +778,12 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
         size_t bytes = r->det_tmp_bytes;
         HIP_TRY(r, det_sort_pairs(r->d_det_tmp, bytes, r->d_det_keys, r->d_det_keys_sorted, r->d_det_slots, r->d_det_slots_sorted, n,
                                   det_key_bits(r), st));
-        hipLaunchKernelGGL(k_det_gather, dim3(grid_for(n)), dim3(BLOCK), 0, st, r->d_det_keys_sorted, r->d_det_slots_sorted, n,
-                           r->d_det_vals, r->d_light_image);
+        if (r->n_layers > 0)
+            hipLaunchKernelGGL(k_det_gather_layers, dim3(grid_for(n)), dim3(BLOCK), 0, st, r->d_det_keys_sorted, r->d_det_slots_sorted, n,
+                               r->d_det_vals, r->d_light_image, (unsigned)B, layer_row_host(r->lcodes, 1), r->n_layers, r->d_lay_light);
+        else
+            hipLaunchKernelGGL(k_det_gather, dim3(grid_for(n)), dim3(BLOCK), 0, st, r->d_det_keys_sorted, r->d_det_slots_sorted, n,
+                               r->d_det_vals, r->d_light_image);
         HIP_TRY(r, hipGetLastError());
     }
     return CL2_OK;
@@ -779,7 +814,7 @@ int launch_accumulate(cl2_renderer* r, hipStream_t st) {
                         r->d_bkt, r->bkt_M);
     r->acc_clean = false;
     HIP_TRY(r, hipGetLastError());
-    return CL2_OK;
+    return launch_layers_accumulate(r, st);
 }
 
 // `mapped`: the pass ran with the density's slot maps, `pass` = its number (adaptive.hpp)
@@ -793,7 +828,7 @@ int launch_finalize_accumulate(cl2_renderer* r, hipStream_t st, bool mapped = fa
                             r->bkt_M);
     r->acc_clean = false;
     HIP_TRY(r, hipGetLastError());
-    return CL2_OK;
+    return launch_layers_accumulate(r, st);       // (never after a mapped pass: launch_resolve refuses a density while a table is set)
 }
 
 int need_scene(cl2_renderer* r) {
@@ -822,6 +857,18 @@ void free_pixel_state(cl2_renderer* r) {
     dev_free(r, r->d_agg); dev_free(r, r->d_light_image); dev_free(r, r->d_finalized); dev_free(r, r->d_uni);
     dev_free(r, r->d_sample_w); dev_free(r, r->d_block_stats);
     for (int q = 0; q < 3; q++) dev_free(r, r->d_map[q]);
+    dev_free(r, r->d_lay_agg); dev_free(r, r->d_lay_light);
+}
+
+// the per-entry buffers of the layer table: allocated when the table is set and again by cl2_set_sample_streams
+int alloc_layer_entries(cl2_renderer* r) {
+    if (r->n_layers == 0) return CL2_OK;
+    const size_t B = (size_t)r->B, L = (size_t)r->n_layers;
+    TRY(dev_alloc(r, &r->d_lay_agg, 3 * L * B));
+    TRY(dev_alloc(r, &r->d_lay_light, L * B));
+    HIP_TRY(r, hipMemset(r->d_lay_agg, 0, 3 * L * B * sizeof(float)));
+    HIP_TRY(r, hipMemset(r->d_lay_light, 0, L * B * sizeof(float4)));
+    return CL2_OK;
 }
 
 int alloc_pixel_state(cl2_renderer* r) {
@@ -865,7 +912,7 @@ int alloc_pixel_state(cl2_renderer* r) {
     }
     if (!ok) return fail(r, CL2_E_HIP, "device buffer initialisation failed");
     r->cur = 0;
-    return CL2_OK;
+    return alloc_layer_entries(r);
 }
 
 #define STAGE_PROLOGUE(r)                 \
@@ -1344,8 +1391,10 @@ int cl2_reset_accumulators(cl2_renderer* r) {
     if (r->d_bkt) HIP_TRY(r, hipMemset(r->d_bkt, 0, 4 * (size_t)r->bkt_M * (size_t)r->FB * sizeof(float)));
     if (r->d_cam_count) HIP_TRY(r, hipMemset(r->d_cam_count, 0, (size_t)r->FB * sizeof(unsigned)));
     r->cam_uniform = 0;
+    if (r->d_lacc) HIP_TRY(r, hipMemset(r->d_lacc, 0, 3 * (size_t)r->n_layers * (size_t)r->FB * sizeof(float)));
     r->mom_valid = r->d_mom != nullptr;
     r->bkt_valid = r->d_bkt != nullptr;
+    r->lay_valid = r->n_layers > 0;
     r->acc_clean = true;
     r->samples = 0;
     return CL2_OK;
@@ -1365,6 +1414,7 @@ int cl2_write_accumulators_packed(cl2_renderer* r, const float* src, size_t n) {
     r->acc_clean = false;
     r->mom_valid = false;                // until cl2_write_moments_packed brings the moments that go with these sums
     r->bkt_valid = false;                // ... and cl2_write_buckets_packed the buckets
+    r->lay_valid = false;                // ... and cl2_write_layers_packed the layer accumulators
     return CL2_OK;
 }
 
@@ -1796,6 +1846,8 @@ int cl2_set_debug_flags(cl2_renderer* r, int flags) {
         return fail(r, CL2_E_INVALID, "debug bits 13 and 14 are A/B switches of the closest-hit walk; the seeded connection query has no such form: cl2_set_connection_query(0) first");
     if (((flags >> 4) & 7) == 7 && r->strategy_mask != CL2_STRATEGY_ALL)
         return fail(r, CL2_E_INVALID, "the cross-check resolve kernel (debug bits 4-6 = 7) has no masked form: set the full strategy mask first");
+    if (((flags >> 4) & 7) == 7 && r->n_layers > 0)
+        return fail(r, CL2_E_INVALID, "the cross-check resolve kernel (debug bits 4-6 = 7) has no layered form: cl2_set_layers(NULL, 0) first");
     r->debug_flags = flags;
     r->bvh.n_fast_nodes = ((flags >> 7) & 1) ? 0 : r->n_fast;      // bit 7: walk the full table (A/B of the pruned one)
     r->bvh.fast_flat = flat_walk(r);     // bit 11: per-lane walk of a flat pruned table (A/B of the wave-uniform one); bit 26: its clamped loop
@@ -1821,6 +1873,8 @@ int cl2_set_strategy_mask(cl2_renderer* r, uint64_t mask) {
     mask &= CL2_STRATEGY_ALL;
     if (mask != CL2_STRATEGY_ALL && ((r->debug_flags >> 4) & 7) == 7)
         return fail(r, CL2_E_INVALID, "the cross-check resolve kernel (debug bits 4-6 = 7) has no masked form: clear debug bits 4-6 first");
+    if (mask != CL2_STRATEGY_ALL && r->n_layers > 0)
+        return fail(r, CL2_E_STATE, "a partial strategy mask and layer accumulators exclude each other (the layers are the masked renders): cl2_set_layers(NULL, 0) first");
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
     r->strategy_mask = mask;
@@ -1829,6 +1883,91 @@ int cl2_set_strategy_mask(cl2_renderer* r, uint64_t mask) {
 int cl2_get_strategy_mask(const cl2_renderer* r, uint64_t* mask_out) {
     if (!r || !mask_out) return CL2_E_INVALID;
     *mask_out = r->strategy_mask;
+    return CL2_OK;
+}
+
+/* Layer accumulators (include/clive2_amd.h, layers.hpp).  The table is what launch_resolve, launch_accumulate and
+ * launch_finalize_accumulate read; lay_valid follows the rules of mom_valid. */
+namespace {
+void free_layers(cl2_renderer* r) {
+    dev_free(r, r->d_lay_agg); dev_free(r, r->d_lay_light); dev_free(r, r->d_lacc);
+    r->n_layers = 0;
+    r->lcodes = LayerCodes{};
+    r->lay_valid = false;
+}
+int need_layers(cl2_renderer* r, size_t n_floats) {
+    if (r->n_layers == 0) return fail(r, CL2_E_STATE, "no layer table is set (cl2_set_layers)");
+    if (n_floats != 3 * (size_t)r->n_layers * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed layer accumulators hold n_layers*3*W*H floats");
+    return CL2_OK;
+}
+}  // namespace
+int cl2_set_layers(cl2_renderer* r, const uint64_t* masks, int n_layers) {
+    static_assert(CL2_MAX_LAYERS == LAYERS_MAX, "CL2_MAX_LAYERS");
+    if (!r) return CL2_E_INVALID;
+    if (n_layers < 0) return fail(r, CL2_E_INVALID, "layers: n_layers must be >= 0");
+    if (n_layers > CL2_MAX_LAYERS) return fail(r, CL2_E_INVALID, "layers: at most CL2_MAX_LAYERS (8) layers; merge layers or render the rest in a second pass over the same seeds");
+    if (n_layers > 0 && !masks) return fail(r, CL2_E_INVALID, "layers: NULL masks with n_layers > 0");
+    if (!masks) n_layers = 0;
+    uint64_t m[CL2_MAX_LAYERS] = {};
+    uint64_t seen = 0;
+    for (int l = 0; l < n_layers; l++) {
+        m[l] = masks[l] & CL2_STRATEGY_ALL;
+        if (m[l] & seen) return fail(r, CL2_E_INVALID, "layers: the masks must be pairwise disjoint (a pair adds to at most one layer)");
+        seen |= m[l];
+    }
+    if (n_layers > 0) {
+        if (r->strategy_mask != CL2_STRATEGY_ALL)
+            return fail(r, CL2_E_STATE, "layer accumulators and a partial strategy mask exclude each other: cl2_set_strategy_mask(CL2_STRATEGY_ALL) first");
+        if (r->density || r->adaptive)
+            return fail(r, CL2_E_STATE, "layer accumulators have no form for a sample density: cl2_set_sample_density(NULL) and cl2_set_adaptive_sampling(0) first");
+        if (((r->debug_flags >> 4) & 7) == 7)
+            return fail(r, CL2_E_INVALID, "the cross-check resolve kernel (debug bits 4-6 = 7) has no layered form: clear debug bits 4-6 first");
+    }
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    if (n_layers == r->n_layers && std::equal(m, m + n_layers, r->layer_masks)) return CL2_OK;      // the table it has
+    free_layers(r);
+    if (n_layers == 0) return CL2_OK;
+    LayerCodes lc{};
+    for (int l = 0; l < n_layers; l++)
+        for (int t = 1; t <= 6; t++)
+            for (int s = 0; s <= 6; s++)
+                if (m[l] & CL2_STRATEGY_BIT(s, t)) lc.w[(t - 1) >> 1] |= (unsigned long long)(l + 1) << (((t - 1) & 1) * 32 + 4 * s);
+    lc.n_layers = n_layers;
+    r->n_layers = n_layers;
+    int rc = alloc_layer_entries(r);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_lacc, 3 * (size_t)n_layers * (size_t)r->FB);
+    if (rc == CL2_OK && hipMemset(r->d_lacc, 0, 3 * (size_t)n_layers * (size_t)r->FB * sizeof(float)) != hipSuccess)
+        rc = fail(r, CL2_E_HIP, "layer accumulators: initialisation failed");
+    if (rc != CL2_OK) { const std::string why = r->err; free_layers(r); return fail(r, rc, why + " (layers are off)"); }
+    std::copy(m, m + CL2_MAX_LAYERS, r->layer_masks);
+    r->lcodes = lc;
+    r->lay_valid = r->acc_clean;         // samples rendered without this table: invalid until cl2_reset_accumulators
+    return CL2_OK;
+}
+int cl2_get_layers(const cl2_renderer* r, uint64_t* masks_out, int capacity) {
+    if (!r || capacity < 0 || (capacity > 0 && !masks_out)) return CL2_E_INVALID;
+    for (int l = 0; l < r->n_layers && l < capacity; l++) masks_out[l] = r->layer_masks[l];
+    return r->n_layers;
+}
+int cl2_read_layers_packed(cl2_renderer* r, float* dst, size_t n_floats) {
+    if (!r || !dst) return CL2_E_INVALID;
+    TRY(need_layers(r, n_floats));
+    if (!r->lay_valid)
+        return fail(r, CL2_E_STATE, "the layer accumulators do not cover every sample in the accumulators (the table was set or changed after "
+                                    "samples, or accumulators were written without them): cl2_reset_accumulators or cl2_write_layers_packed");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(dst, r->d_lacc, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+int cl2_write_layers_packed(cl2_renderer* r, const float* src, size_t n_floats) {
+    if (!r || !src) return CL2_E_INVALID;
+    TRY(need_layers(r, n_floats));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(r->d_lacc, src, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    r->lay_valid = true;
     return CL2_OK;
 }
 
@@ -2688,6 +2827,7 @@ int cl2_run_until(cl2_renderer* r, double target, double floor, int min_passes, 
 int cl2_set_sample_density(cl2_renderer* r, const float* density, size_t n) {
     if (!r) return CL2_E_INVALID;
     TRY(no_comm(r));
+    if (density && r->n_layers > 0) return fail(r, CL2_E_STATE, "a sample density and layer accumulators exclude each other (no mapped form): cl2_set_layers(NULL, 0) first");
     if (density) {
         if (n != (size_t)r->FB) return fail(r, CL2_E_INVALID, "the density holds W*H weights");
         for (size_t i = 0; i < n; i++)
@@ -2718,6 +2858,7 @@ int cl2_update_sample_density(cl2_renderer* r, double floor, double uniform_shar
     if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
     if (!(uniform_share > 0.0 && uniform_share <= 1.0)) return fail(r, CL2_E_INVALID, "uniform_share must be in (0, 1]");
     TRY(no_comm(r));
+    if (r->n_layers > 0) return fail(r, CL2_E_STATE, "a sample density and layer accumulators exclude each other (no mapped form): cl2_set_layers(NULL, 0) first");
     TRY(need_moments(r));
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
@@ -2729,6 +2870,7 @@ int cl2_set_adaptive_sampling(cl2_renderer* r, int on, double uniform_share) {
     if (on != 0 && on != 1) return fail(r, CL2_E_INVALID, "adaptive sampling: 0 off, 1 on");
     if (on && !(uniform_share > 0.0 && uniform_share <= 1.0)) return fail(r, CL2_E_INVALID, "uniform_share must be in (0, 1]");
     if (on) TRY(no_comm(r));
+    if (on && r->n_layers > 0) return fail(r, CL2_E_STATE, "adaptive sampling and layer accumulators exclude each other (no mapped form): cl2_set_layers(NULL, 0) first");
     r->adaptive = on != 0;
     if (on) r->adaptive_share = uniform_share;
     return CL2_OK;

@@ -39,7 +39,10 @@ def _write_layers(renderer, args, K):
     """--layers: the three layer pictures, tone-mapped with the log-average of their SUM so that their brightness is comparable."""
     t0 = time.time()
     try:
-        layers = renderer.render_layers(-(-args.samples // K))
+        if args.single_pass:
+            layers = renderer.render_layers_once(-(-args.samples // K))
+        else:
+            layers = renderer.render_layers(-(-args.samples // K))
     finally:
         renderer.close()
     print(f"[rank 0] rendering {len(layers)} layers took {time.time() - t0:.2f} seconds")
@@ -116,6 +119,9 @@ def main(argv=None):
                     help="render the emission / direct / indirect layers (Renderer.render_layers, one render of --samples each from "
                          "the same seeds) and write PREFIX_emission.png, PREFIX_direct.png, PREFIX_indirect.png, tone-mapped with "
                          "the log-average of their sum, and PREFIX_layers.npz with the float pictures (one rank only)")
+    ap.add_argument("--single-pass", action="store_true",
+                    help="with --layers: write the same pictures from ONE render with per-layer accumulators "
+                         "(Renderer.render_layers_once, DESIGN.md 6.12) instead of one render per layer")
     args = ap.parse_args(argv)
     # refused before any renderer is made
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
@@ -149,6 +155,8 @@ def main(argv=None):
             strategy_mask = strategies.parse_path_length(args.path_length)
     except ValueError as e:
         ap.error(str(e))
+    if args.single_pass and args.layers is None:
+        ap.error("--single-pass is a way to render --layers: give --layers PREFIX")
     if args.layers is not None:
         if strategy_mask is not None:
             ap.error("--layers sets the strategy mask of each layer itself: it does not go with --strategies or --path-length")

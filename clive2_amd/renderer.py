@@ -526,6 +526,75 @@ class Renderer:
             self.set_strategy_mask(found)
         return out
 
+    # ---- layer accumulators (cl2_set_layers, csrc/layers.hpp) ----
+    def set_layers(self, layers=None):
+        """Fill one colour accumulator per layer of `layers` ({name: mask or pairs}, at most 8, pairwise disjoint) in every pass,
+        beside the ordinary accumulators, which get the bytes they get without layers.  Layer l receives what rows 0..2 of the
+        accumulators receive in a render with set_strategy_mask(layer l): with set_reproducible(True) the same bytes.  None or an
+        empty dictionary switches the layers off (the default).  The table stays until it is set again; setting another one on a
+        handle that holds samples invalidates the layer accumulators until reset_accumulators().  Not together with a partial
+        strategy mask, a sample density / adaptive sampling or the cross-check resolve kernel."""
+        items = dict(layers or {})
+        masks = strategies.layer_masks(items)                 # refused before the library sees anything
+        arr = (C.c_uint64 * max(len(masks), 1))(*masks)
+        self._check(self._L.cl2_set_layers(self._h, arr if masks else None, len(masks)), "cl2_set_layers")
+        self._layer_names = list(items)
+
+    def layers(self):
+        """{name: mask} of the table that is set ({} = off); layers set through the C ABI alone are named layer0, layer1, ..."""
+        m = (C.c_uint64 * strategies.MAX_LAYERS)()
+        n = self._L.cl2_get_layers(self._h, m, strategies.MAX_LAYERS)
+        if n < 0:
+            self._check(n, "cl2_get_layers")
+        names = getattr(self, "_layer_names", [])
+        if len(names) != n:
+            names = [f"layer{l}" for l in range(n)]
+        return {names[l]: int(m[l]) for l in range(n)}
+
+    def layer_accumulators(self):
+        """The layer accumulators, float32 (L, 3, W*H): per layer the b, g, r planes, packed like rows 0..2 of
+        packed_accumulators().  RendererError while they are invalid or no table is set."""
+        n = len(self.layers())
+        a = np.empty((n, 3, self.batch_size), np.float32)
+        self._check(self._L.cl2_read_layers_packed(self._h, ptr(a), C.c_size_t(a.size)), "cl2_read_layers_packed")
+        return a
+
+    def load_layer_accumulators(self, a):
+        """Write the layer accumulators (checkpoints: after load_packed_accumulators, which invalidates them)."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        self._check(self._L.cl2_write_layers_packed(self._h, ptr(a), C.c_size_t(a.size)), "cl2_write_layers_packed")
+
+    def layer_radiance(self):
+        """{name: (H, W, 3) float32, BGR}: layer accumulator / summed_sample_weights, scrubbed -- `radiance` of the render masked
+        with the layer, from the one render that filled the accumulators."""
+        names = list(self.layers())
+        la = self.layer_accumulators()
+        _, wts, _, _ = self.read_accumulators()
+        H, W = self.pixel_height, self.pixel_width
+        out = {}
+        for l, name in enumerate(names):
+            img = np.ascontiguousarray(la[l].reshape(3, H, W).transpose(1, 2, 0))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out[name] = np.nan_to_num(img / wts, neginf=0, posinf=0)
+        return out
+
+    def render_layers_once(self, passes, layers=strategies.LAYERS, seeds=None):
+        """The dictionary render_layers returns, from ONE render: reset_accumulators(), set_seeds(seeds), set_layers(layers),
+        run_samples(passes), layer_radiance().  `seeds`: as set_seeds; None = the handle's current seeds.  The layer table found on
+        entry is restored; the accumulators are left holding the full picture of the render."""
+        start = self.get_random_buffer() if seeds is None else np.array(seeds, dtype=np.uint32, copy=True)
+        table = dict(layers)
+        strategies.layer_masks(table)                          # refused before anything is rendered
+        found = self.layers()
+        try:
+            self.reset_accumulators()
+            self.set_seeds(start)
+            self.set_layers(table)
+            self.run_samples(passes)
+            return self.layer_radiance()
+        finally:
+            self.set_layers(found)
+
     def set_subpath_gather(self, lanes=0, wait_steps=0):
         """Whole-subpath launch: lanes gathered / steps waited before a wave runs its bounce phase (0 = default)."""
         self._check(self._L.cl2_set_subpath_gather(self._h, int(lanes), int(wait_steps)), "set_subpath_gather")

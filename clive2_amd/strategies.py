@@ -63,6 +63,27 @@ LAYERS = {"emission": path_length(1, 1), "direct": path_length(2, 2), "indirect"
 SINGLETONS = {f"s{s}t{t}": bit(s, t) for s, t in PAIRS}    # render_layers(passes, SINGLETONS) is the pyramid
 
 
+MAX_LAYERS = 8     # CL2_MAX_LAYERS (include/clive2_amd.h)
+
+
+def layer_masks(layers):
+    """The layer table of cl2_set_layers: {name: mask or pairs} -> the list of masks in the dictionary's order, bits outside the 41
+    dropped.  ValueError for more than MAX_LAYERS layers or for layers that share a pair (a pair adds to at most one layer); an
+    empty layer and pairs in no layer are fine.  Needs no renderer."""
+    items = list(dict(layers).items())
+    if len(items) > MAX_LAYERS:
+        raise ValueError(f"{len(items)} layers: a layer table holds at most {MAX_LAYERS}")
+    out, seen = [], {}
+    for name, m in items:
+        m = to_mask(m) & ALL
+        for s, t in pairs(m):
+            if (s, t) in seen:
+                raise ValueError(f"layers {seen[(s, t)]!r} and {name!r} share the pair ({s}, {t}): layers must be disjoint")
+            seen[(s, t)] = name
+        out.append(m)
+    return out
+
+
 def _int(text, what):
     text = text.strip()
     if not text or not text.isdigit():

@@ -642,6 +642,40 @@ int cl2_picture_tone_map(cl2_renderer* r, double exposure, double white_point, d
 int cl2_set_strategy_mask(cl2_renderer* r, uint64_t mask);
 int cl2_get_strategy_mask(const cl2_renderer* r, uint64_t* mask_out);
 
+/* ---- layer accumulators: the layers of ONE render (csrc/layers.hpp, csrc/connect_resolve.hpp LAYERS) ----
+ * A layer table assigns each of the 41 (s, t) pairs to at most one of n_layers <= CL2_MAX_LAYERS layers: masks[l] is the mask of
+ * layer l in the bit layout of cl2_set_strategy_mask (pair (s, t) = bit (t - 1) * 7 + s; bits outside the 41 are dropped).  The masks
+ * must be pairwise disjoint (else CL2_E_INVALID); they need not cover all pairs (a pair in no layer adds to no layer) and an empty
+ * mask is a legal layer whose accumulator stays +0.  NULL / 0 switches the table off (the default).
+ * While a table is set, every pass fills the ordinary accumulators, moments, buckets, seeds and ray counters with the bytes of a
+ * pass without one, and additionally L colour accumulators lacc[L][3][W*H] (b, g, r): lacc[l] receives what rows 0..2 of the
+ * accumulators receive in a render with cl2_set_strategy_mask(masks[l]) -- the same float operations on the same operands in the
+ * same order, so with cl2_set_reproducible(1) the same bytes, and with float atomics the same sums in the hardware's order.  The
+ * picture of layer l is nan_to_num(lacc[l] / accumulator row 3): the denominator is shared, which is why layers that partition the 41
+ * pairs add up to the full picture, to float rounding.
+ * Memory while set: 24 (+ 4 unused) bytes per layer and entry (streams x W x H), 12 per layer and pixel.  The per-entry buffers are
+ * allocated by cl2_set_layers and again by cl2_set_sample_streams; the table survives cl2_upload_scene, cl2_set_sample_streams and
+ * cl2_reset_accumulators, which zeroes lacc.
+ * Validity follows the moment buffer's rule: lacc is valid only if every sample in the ordinary accumulators since their last reset
+ * was rendered under this table.  Setting a DIFFERENT table on a handle that holds samples zeroes lacc and marks it invalid until
+ * cl2_reset_accumulators (setting the table it already has changes nothing); so does cl2_write_accumulators_packed, until
+ * cl2_write_layers_packed, which makes it valid.  cl2_read_layers_packed returns CL2_E_STATE while invalid or without a table.
+ * n_floats = n_layers * 3 * W * H, layer-major, then b, g, r planes (else CL2_E_INVALID).  cl2_get_layers writes up to `capacity`
+ * masks and returns n_layers.
+ * Refused, whichever call comes second (CL2_E_STATE or CL2_E_INVALID, the earlier setting is kept, the message names the way out):
+ * a table together with a partial strategy mask; with a sample density or adaptive sampling (there is no mapped form); with debug
+ * bits 4-6 = 7 (the cross-check resolve kernel); more than CL2_MAX_LAYERS layers.  Error tracking, robust buckets, the
+ * reproducible switch, sample streams, every traversal organisation, pipelining and the visibility-query walk combine with a table
+ * and describe the full picture as before.
+ * OUT OF SCOPE: cl2_reduce_accumulators neither reduces nor refuses the layer accumulators -- a multi-rank host sums
+ * cl2_read_layers_packed itself (every rank must set the same table).  There are no per-layer moments, buckets or denoisers and no
+ * device tone map of layer pictures.  No reference counterpart (src/trace.metal:649-825 sums all pairs). */
+#define CL2_MAX_LAYERS 8
+int cl2_set_layers(cl2_renderer* r, const uint64_t* masks, int n_layers);          /* NULL / 0 = off (the default) */
+int cl2_get_layers(const cl2_renderer* r, uint64_t* masks_out, int capacity);      /* returns n_layers */
+int cl2_read_layers_packed(cl2_renderer* r, float* host_dst, size_t n_floats);     /* [L][3][W*H], b g r */
+int cl2_write_layers_packed(cl2_renderer* r, const float* host_src, size_t n_floats);
+
 #ifdef __cplusplus
 }
 #endif

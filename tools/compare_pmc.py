@@ -19,7 +19,10 @@ RENAMED = {"k_finalize_accumulate": "k_finalize_accumulate<false>", "k_accumulat
               for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true")},
            # r19: the resolve kernel gained a STRAT parameter (strategy mask); the render runs <..., false>
            **{f"k_connect_resolve<{a},{m}>": f"k_connect_resolve<{a},{m},false>"
-              for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true") for m in ("false", "true")}}
+              for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true") for m in ("false", "true")},
+           # r20: the resolve kernel gained a LAYERS parameter (layer accumulators); the render runs <..., false>
+           **{f"k_connect_resolve<{a},{m},{s}>": f"k_connect_resolve<{a},{m},{s},false>"
+              for a in ("3,true,false", "2,false,false", "2,true,true", "2,false,true") for m in ("false", "true") for s in ("false", "true")}}
 
 
 def kernels(tag, workload):
