@@ -7,6 +7,7 @@
 // the host between samples.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -43,11 +44,6 @@ thread_local std::string g_create_error;
 
 enum Stage { ST_GENERATE, ST_TRAVERSE_PATHS, ST_BOUNCE, ST_CONNECT_SETUP, ST_TRAVERSE_CONN, ST_CONNECT_RESOLVE,
              ST_FINALIZE, ST_ACCUMULATE, ST_COUNT };
-
-template <typename T> struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-};
 
 }  // namespace
 
@@ -230,6 +226,28 @@ template <typename T> void dev_free(cl2_renderer* r, T*& p) {
     p = nullptr;
 }
 
+// a device buffer that lives as long as one call: allocated through dev_alloc, released when the call returns, whichever way
+template <typename T> struct Scratch {
+    cl2_renderer* r;
+    T* p = nullptr;
+    explicit Scratch(cl2_renderer* r_) : r(r_) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { dev_free(r, p); }
+    int alloc(size_t count) { return dev_alloc(r, &p, count); }
+    operator T*() const { return p; }
+};
+
+// Run-time flags as template arguments: with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...).
+// f is instantiated for every combination, so a kernel launch inside it stands under an `if constexpr` that names the
+// combinations that exist: no other kernel is emitted.  Template parameters that are no flags stay branches at the call site.
+template <class F> void with_flags(F&& f) { f(); }
+template <class F, class... Rest> void with_flags(F&& f, bool flag, Rest... rest) {
+    if (flag) with_flags([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_flags([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+template <int N> using int_c = std::integral_constant<int, N>;
+
 // device copy of n host elements (a scene array)
 template <typename T> int upload(cl2_renderer* r, T** p, const T* h, size_t n) {
     TRY(dev_alloc(r, p, n));
@@ -299,13 +317,10 @@ int launch_generate(cl2_renderer* r, int which, hipStream_t st, const PathBufs* 
 // `map`: the set's slot -> pixel map of a mapped pass (adaptive.hpp), nullptr = the default kernels
 int launch_generate_both(cl2_renderer* r, hipStream_t st, const PathBufs* set, const int* map) {
     Timed t(r, ST_GENERATE, st);
-    if (map)
-        hipLaunchKernelGGL(k_gen_rays<true>, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->d_light_tris, r->d_light_areas,
+    with_flags([&](auto MAPPED) {
+        hipLaunchKernelGGL(k_gen_rays<MAPPED.value>, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->d_light_tris, r->d_light_areas,
                            r->d_light_tri_index, r->d_mats, r->light_count, r->cam, r->d_seeds, set[CL2_LIGHT], set[CL2_CAMERA], map);
-    else
-        hipLaunchKernelGGL(k_gen_rays<false>, dim3(grid_for(r->B)), dim3(BLOCK), 0, st, r->B, r->d_light_tris, r->d_light_areas,
-                           r->d_light_tri_index, r->d_mats, r->light_count, r->cam, r->d_seeds, set[CL2_LIGHT], set[CL2_CAMERA],
-                           (const int*)nullptr);
+    }, map != nullptr);
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
 }
@@ -446,7 +461,7 @@ int launch_wide(cl2_renderer* r, hipStream_t st, int stage, const unsigned* coun
     w.overflow = r->d_wide_ovf + (size_t)stage * persistent_grid() * BLOCK * w.ovf_stride;
     // LDS per workgroup: per-lane stack (8 B per entry and lane) + the top of the tree (128 B per wide node); experiment
     // switches: debug_flags bits 16-19 stack entries (0 = default), bits 20-23 window in units of 32 wide nodes
-    const int sflag = (r->debug_flags >> 16) & 0xF, wflag = (r->debug_flags >> 20) & 0xF;
+    const int wflag = (r->debug_flags >> 20) & 0xF;
     // (round 3 ran 7 stack entries + a 64-node window, 22 KB per workgroup; its measurements are in DESIGN.md 6.1)
     // round 4: WIDE_STACK_LDS (8) entries, a compile-time constant (shift-addressed).  The window's lanes read LDS in a
     // branch of their own (the per-lane pointer select of round 3 made EVERY node fetch a flat load).  Same-box A/B of the
@@ -456,7 +471,6 @@ int launch_wide(cl2_renderer* r, hipStream_t st, int stage, const unsigned* coun
     //   interior  8+0 12.0 | 24.2   8+32 11.2 | 22.8   7+64 11.2 | 23.3   8+64 11.2 | 22.3; one triangle pair per pass: 8+64 10.7 | 21.3
     // so: 32 nodes (20 KB per workgroup: 8 workgroups per CU) and two pairs per pass while the tree is cache-resident, 64
     // nodes and one pair when it streams from memory.  debug_flags bits 20-23 override the window (units of 32 nodes, 15 = none).
-    (void)sflag;
     const bool streams_from_memory = !two_tris_per_step_plain(r);
     w.stack_lds = WIDE_STACK_LDS;
     w.n_lds_nodes = std::min(r->n_wide, wflag == 15 ? 0 : (wflag ? 32 * wflag : (streams_from_memory ? 64 : 32)));
@@ -466,28 +480,37 @@ int launch_wide(cl2_renderer* r, hipStream_t st, int stage, const unsigned* coun
     // the binary records (lanes whose ray has a non-finite 1/d) come through the caches: no window for them
     BvhView b = r->bvh;
     b.n_lds_nodes = 0; b.lds_tris = 0; b.n_fast_nodes = 0;
-#define CL2_WIDE(REPS, TALLY, SPEC, PACK, ORDER) \
-    hipLaunchKernelGGL((k_traverse_wide<REPS, Source, TALLY, SPEC, PACK, ORDER, VIS>), dim3(grid), dim3(BLOCK), lds, st, w, b, count, work_counter, src, stats, is_conn)
-// (a macro argument may not be a run-time value: one dispatch level per template parameter)
-#define CL2_WIDE_BY_SPEC(REPS, TALLY, PACK) do { if (spec) CL2_WIDE(REPS, TALLY, true, PACK, false); else CL2_WIDE(REPS, TALLY, false, PACK, false); } while (0)
-#define CL2_WIDE_BY_TALLY(REPS, PACK) do { \
-        if constexpr (VIS) { if (tally) CL2_WIDE(REPS, true, true, PACK, false); else CL2_WIDE(REPS, false, true, PACK, false); } \
-        else if (r->traversal_order != 0) { if (tally) CL2_WIDE(REPS, true, true, PACK, true); else CL2_WIDE(REPS, false, true, PACK, true); } \
-        else if (tally) CL2_WIDE_BY_SPEC(REPS, true, PACK); else CL2_WIDE_BY_SPEC(REPS, false, PACK); } while (0)
-    [[maybe_unused]] const bool spec = !((r->debug_flags >> 13) & 1);            // speculative expansion of the stack top (bvh_wide.hpp); bit 13: off
+    // The opt-in nearest-first child order (cl2_set_traversal_order; NOT the parity path) exists for the speculative walk only, and
+    // so does the seeded walk, which keeps the reference's order.
+    const bool order = !VIS && r->traversal_order != 0;
+    const bool spec = VIS || order || !((r->debug_flags >> 13) & 1);            // speculative expansion of the stack top (bvh_wide.hpp); bit 13: off
     // 36-byte triangle records, a pair fetched as one run of 72 bytes (bvh_wide.hpp: PACK); bit 14: the 48-byte records of the other
-    // walks.  The opt-in nearest-first child order (cl2_set_traversal_order; NOT the parity path) exists for the speculative walk only.
+    // walks.
     const bool pack = w.tris36 && !((r->debug_flags >> 14) & 1);
-    if constexpr (std::is_same_v<Source, ConnVisRaySource>) {
-        // the seeded connection launch exists for the tree's own record form only: bit 14 is an A/B switch of the closest-hit walk and
-        // is refused together with cl2_set_connection_query(1) (its 48-byte instantiation with one pair per pass would spill)
-        if (!pack) return fail(r, CL2_E_STATE, "the seeded connection walk reads the packed triangle records");
-        if (streams_from_memory) CL2_WIDE_BY_TALLY(1, true); else CL2_WIDE_BY_TALLY(WIDE_TRI_REPS, true);
-    } else if (streams_from_memory) { if (pack) CL2_WIDE_BY_TALLY(1, true); else CL2_WIDE_BY_TALLY(1, false); }
-    else { if (pack) CL2_WIDE_BY_TALLY(WIDE_TRI_REPS, true); else CL2_WIDE_BY_TALLY(WIDE_TRI_REPS, false); }
-#undef CL2_WIDE_BY_TALLY
-#undef CL2_WIDE_BY_SPEC
-#undef CL2_WIDE
+    constexpr bool seeded_conn = std::is_same_v<Source, ConnVisRaySource>;
+    // the seeded connection launch exists for the tree's own record form only: bit 14 is an A/B switch of the closest-hit walk and
+    // is refused together with cl2_set_connection_query(1) (its 48-byte instantiation with one pair per pass would spill)
+    if (seeded_conn && !pack) return fail(r, CL2_E_STATE, "the seeded connection walk reads the packed triangle records");
+    auto launch = [&](auto REPS) {
+        with_flags([&](auto TALLY, auto SPEC, auto PACK, auto ORDER) {
+            if constexpr ((SPEC.value || !(ORDER.value || VIS)) && !(ORDER.value && VIS) && (PACK.value || !seeded_conn))
+                hipLaunchKernelGGL((k_traverse_wide<REPS.value, Source, TALLY.value, SPEC.value, PACK.value, ORDER.value, VIS>), dim3(grid),
+                                   dim3(BLOCK), lds, st, w, b, count, work_counter, src, stats, is_conn);
+        }, tally, spec, pack, order);
+    };
+    if (streams_from_memory) launch(int_c<1>{}); else launch(int_c<WIDE_TRI_REPS>{});
+    HIP_TRY(r, hipGetLastError());
+    return CL2_OK;
+}
+
+// One persistent launch of the binary walk (k_traverse_persistent) over the rays of `src`: the subpath levels and the connection rays
+// of trees that are not LDS-resident, where the 4-wide walk steps aside.
+template <class Source>
+int launch_persistent(cl2_renderer* r, hipStream_t st, int grid, const unsigned* count, unsigned* work_counter, Source src, int is_conn) {
+    with_flags([&](auto CNT, auto TWO) {
+        hipLaunchKernelGGL((k_traverse_persistent<CNT.value, TWO.value, Source>), dim3(grid), dim3(BLOCK), bvh_lds_bytes(r), st, r->bvh,
+                           count, work_counter, src, r->d_stats, is_conn);
+    }, count_ref(r), two_tris_per_step(r));
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
 }
@@ -524,36 +547,25 @@ int launch_trace(cl2_renderer* r, int which, hipStream_t st, const PathBufs* set
             // pass the walk is ahead alone as well -- serial order at 3840 x 2160, subpath traversal per sample: blob 15.8 -> 12.6
             // ms, 1M triangles 44.2 -> 31.8 -- and with sample streams a launch is no longer all tail.  (debug_flags bit 3, which
             // forced it in the serial order, is accepted and has no effect any more; mode 2 still means the binary walk.)
+            unsigned* const work = r->d_work + first * WORK_STRIDE;
             if (wide_walk(r)) {
-                if (merged) TRY(launch_wide(r, st, 0, c_trav, r->d_work + first * WORK_STRIDE, dual, 0));
-                else TRY(launch_wide(r, st, 0, c_trav, r->d_work + first * WORK_STRIDE, src, 0));
-                r->launches_tp++;
+                if (merged) TRY(launch_wide(r, st, 0, c_trav, work, dual, 0));
+                else TRY(launch_wide(r, st, 0, c_trav, work, src, 0));
             } else {
-#define CL2_PERSIST(CNT, TWO, SRCT, SRC)                                                                                   \
-            hipLaunchKernelGGL((k_traverse_persistent<CNT, TWO, SRCT>), dim3(persistent_grid_paths(r)), dim3(BLOCK), bvh_lds_bytes(r), \
-                               st, r->bvh, c_trav, r->d_work + first * WORK_STRIDE, SRC, r->d_stats, 0)
-#define CL2_PERSIST_SRC(SRCT, SRC)                                                                                         \
-            do {                                                                                                           \
-                if (two_tris_per_step(r)) { if (count_ref(r)) CL2_PERSIST(true, true, SRCT, SRC); else CL2_PERSIST(false, true, SRCT, SRC); } \
-                else { if (count_ref(r)) CL2_PERSIST(true, false, SRCT, SRC); else CL2_PERSIST(false, false, SRCT, SRC); }       \
-            } while (0)
-            if (merged) CL2_PERSIST_SRC(DualPathRaySource, dual); else CL2_PERSIST_SRC(PathRaySource, src);
-#undef CL2_PERSIST_SRC
-#undef CL2_PERSIST
-            r->launches_tp++;
-            HIP_TRY(r, hipGetLastError());
+                if (merged) TRY(launch_persistent(r, st, persistent_grid_paths(r), c_trav, work, dual, 0));
+                else TRY(launch_persistent(r, st, persistent_grid_paths(r), c_trav, work, src, 0));
             }
+            r->launches_tp++;
         }
         Timed t(r, split ? ST_BOUNCE : ST_TRAVERSE_PATHS, st);
         const float4* ext_hit = hits_ready ? r->d_hit_cam0 : r->d_hit;
-#define CL2_TRACE(CAM, CNT, EXT)                                                                                          \
-        hipLaunchKernelGGL((k_trace_subpath<CAM, CNT, EXT>), dim3(grid_for(B)), dim3(BLOCK), (EXT) ? 0 : bvh_lds_bytes(r), st, r->bvh, r->d_stats, \
-                           first, end, q_in, c_in, q_out, c_out, B, pb, r->d_seeds, r->d_tri_shade, r->d_mats, r->n_mats,        \
-                           r->d_block_stats, ext_hit)
-        if (split) { if (which == CL2_CAMERA) CL2_TRACE(true, false, true); else CL2_TRACE(false, false, true); }
-        else if (which == CL2_CAMERA) { if (count_ref(r)) CL2_TRACE(true, true, false); else CL2_TRACE(true, false, false); }
-        else { if (count_ref(r)) CL2_TRACE(false, true, false); else CL2_TRACE(false, false, false); }
-#undef CL2_TRACE
+        // EXT: the bounce of a level whose hits a traversal launch left in ext_hit; the reference walk's tallies are then that launch's
+        with_flags([&](auto CAM, auto CNT, auto EXT) {
+            if constexpr (!(EXT.value && CNT.value))
+                hipLaunchKernelGGL((k_trace_subpath<CAM.value, CNT.value, EXT.value>), dim3(grid_for(B)), dim3(BLOCK),
+                                   EXT.value ? 0 : bvh_lds_bytes(r), st, r->bvh, r->d_stats, first, end, q_in, c_in, q_out, c_out, B, pb,
+                                   r->d_seeds, r->d_tri_shade, r->d_mats, r->n_mats, r->d_block_stats, ext_hit);
+        }, which == CL2_CAMERA, !split && count_ref(r), split);
         if (!split) r->launches_tp++;
         HIP_TRY(r, hipGetLastError());
     }
@@ -591,14 +603,17 @@ int launch_subpaths(cl2_renderer* r, hipStream_t st, const PathBufs* set, int ki
     // 13.0 -> 13.6 ms on the glass scene, 8 waves 24.5 ms); the grid holds as many workgroups as stay resident
     constexpr int WPS = 5;
     const int grid = std::max(1, persistent_grid_paths(r) * WPS / 8);
-#define CL2_WHOLE(CNT, TWO, WIDE, ...)                                                                                    \
-    hipLaunchKernelGGL((k_subpaths_persistent<CNT, TWO, WPS, WIDE, ##__VA_ARGS__>), dim3(grid), dim3(BLOCK), lds, st, r->bvh, w, \
-                       r->B, r->d_work, set[CL2_LIGHT], set[CL2_CAMERA], r->d_seeds, r->d_tri_shade, r->d_mats, r->n_mats, \
-                       r->d_stats, lanes, wait, kinds)
-    if (widew) { if (two_tris_per_step(r)) CL2_WHOLE(false, true, true, WIDE_TRI_REPS); else CL2_WHOLE(false, true, true, 1); }
-    else if (two_tris_per_step(r)) { if (count_ref(r)) CL2_WHOLE(true, true, false); else CL2_WHOLE(false, true, false); }
-    else { if (count_ref(r)) CL2_WHOLE(true, false, false); else CL2_WHOLE(false, false, false); }
-#undef CL2_WHOLE
+    // the WIDE forms are uncounted (wide_walk) and hold TWO_TRIS at true: what their walk varies is the triangle pairs per pass,
+    // which the binary forms leave at the default
+    auto launch = [&](auto REPS) {
+        with_flags([&](auto CNT, auto TWO, auto WIDE) {
+            if constexpr (WIDE.value ? (!CNT.value && TWO.value) : REPS.value == WIDE_TRI_REPS)
+                hipLaunchKernelGGL((k_subpaths_persistent<CNT.value, TWO.value, WPS, WIDE.value, REPS.value>), dim3(grid), dim3(BLOCK), lds, st,
+                                   r->bvh, w, r->B, r->d_work, set[CL2_LIGHT], set[CL2_CAMERA], r->d_seeds, r->d_tri_shade, r->d_mats,
+                                   r->n_mats, r->d_stats, lanes, wait, kinds);
+        }, !widew && count_ref(r), widew || two_tris_per_step(r), widew);
+    };
+    if (widew && !two_tris_per_step(r)) launch(int_c<1>{}); else launch(int_c<WIDE_TRI_REPS>{});
     r->launches_tp++;
     HIP_TRY(r, hipGetLastError());
     return CL2_OK;
@@ -643,27 +658,15 @@ int launch_connect(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs)
             } else if (wide_walk(r)) {
                 TRY(launch_wide(r, st, 1, r->d_qcount + 7, r->d_work + 7 * WORK_STRIDE, src, 1));
             } else {
-#define CL2_PERSIST(CNT, TWO, SRCT, SRC)                                                                                  \
-            hipLaunchKernelGGL((k_traverse_persistent<CNT, TWO, SRCT>), dim3(persistent_grid_conn(r)), dim3(BLOCK), bvh_lds_bytes(r), \
-                               st, r->bvh, r->d_qcount + 7, r->d_work + 7 * WORK_STRIDE, SRC, r->d_stats, 1)
-#define CL2_PERSIST_SRC(SRCT, SRC)                                                                                        \
-            do {                                                                                                          \
-                if (two_tris_per_step(r)) { if (count_ref(r)) CL2_PERSIST(true, true, SRCT, SRC); else CL2_PERSIST(false, true, SRCT, SRC); } \
-                else { if (count_ref(r)) CL2_PERSIST(true, false, SRCT, SRC); else CL2_PERSIST(false, false, SRCT, SRC); }      \
-            } while (0)
-            CL2_PERSIST_SRC(ConnRaySource, src);
-#undef CL2_PERSIST_SRC
-#undef CL2_PERSIST
+                TRY(launch_persistent(r, st, persistent_grid_conn(r), r->d_qcount + 7, r->d_work + 7 * WORK_STRIDE, src, 1));
             }
         } else {
             // grid-stride over the (device-side) ray count; enough workgroups to fill 256 CUs several times over
             const int grid = std::min<size_t>(grid_for((size_t)B * 8), 256 * 32);
-            if (count_ref(r))
-                hipLaunchKernelGGL(k_traverse_conn<true>, dim3(grid), dim3(BLOCK), bvh_lds_bytes(r), st, r->bvh, B, r->d_qcount + 7, r->d_ctag,
-                                   lp.P0, cp.P0, r->cam, r->d_chit[cs], r->d_stats);
-            else
-                hipLaunchKernelGGL(k_traverse_conn<false>, dim3(grid), dim3(BLOCK), bvh_lds_bytes(r), st, r->bvh, B, r->d_qcount + 7, r->d_ctag,
-                                   lp.P0, cp.P0, r->cam, r->d_chit[cs], r->d_stats);
+            with_flags([&](auto CNT) {
+                hipLaunchKernelGGL(k_traverse_conn<CNT.value>, dim3(grid), dim3(BLOCK), bvh_lds_bytes(r), st, r->bvh, B, r->d_qcount + 7,
+                                   r->d_ctag, lp.P0, cp.P0, r->cam, r->d_chit[cs], r->d_stats);
+            }, count_ref(r));
         }
         r->launches_tc++;
     }
@@ -716,19 +719,9 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
     const PathBufs& cp = set[CL2_CAMERA];
     {
         Timed t(r, ST_CONNECT_RESOLVE, st);
-#define CL2_RESOLVE_S(W, ML, DET, MAPPED, STRAT)                                                                                 \
-        hipLaunchKernelGGL((k_connect_resolve<W, ML, DET, MAPPED, STRAT>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, \
-                           r->cam_tris, r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_agg, r->d_light_image, r->d_uni, r->d_stats, r->debug_flags, \
-                           r->d_det_keys, r->d_det_vals, map, (unsigned long long)r->strategy_mask, r->lcodes, r->d_lay_agg, r->d_lay_light)
-        // a layer table (cl2_set_layers): the LAYERS instantiations, two waves per SIMD (their 24 layer totals are registers)
-#define CL2_RESOLVE_L(ML, DET)                                                                                                   \
-        hipLaunchKernelGGL((k_connect_resolve<2, ML, DET, false, false, true>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, \
-                           r->cam_tris, r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_agg, r->d_light_image, r->d_uni, r->d_stats, r->debug_flags, \
-                           r->d_det_keys, r->d_det_vals, (const int*)nullptr, (unsigned long long)r->strategy_mask, r->lcodes, r->d_lay_agg, r->d_lay_light)
         // a full strategy mask (the default, or set explicitly) runs the kernels without the STRAT code
-#define CL2_RESOLVE_M(W, ML, DET, MAPPED) do { if (masked) CL2_RESOLVE_S(W, ML, DET, MAPPED, true); else CL2_RESOLVE_S(W, ML, DET, MAPPED, false); } while (0)
         const bool masked = r->strategy_mask != CL2_STRATEGY_ALL;
-#define CL2_RESOLVE(W, ML, DET) do { if (layered) CL2_RESOLVE_L(ML, DET); else if (map) CL2_RESOLVE_M(W, ML, DET, true); else CL2_RESOLVE_M(W, ML, DET, false); } while (0)
+        // a layer table (cl2_set_layers): the LAYERS instantiations, two waves per SIMD (their 24 layer totals are registers)
         const bool layered = r->n_layers > 0;
         // 3 waves per SIMD: what 165 VGPRs and 52 KB of LDS tables per workgroup allow (2 / 4 measured slower: DESIGN 6.1).  Debug
         // bits 4-6 = 7: one wave per camera vertex (tests/connect_resolve_wide.hpp: same results bit for bit, measured slower: 1.14 vs
@@ -753,21 +746,31 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
 #else
         if (occ == 7) return fail(r, CL2_E_INVALID, "the one-wave-per-camera-vertex resolve kernel is only built into the test variant of the library");
 #endif
-        // the material table goes to LDS when it fits LDS_MAT_CAP entries (the reference ships 8): connect_resolve.hpp
-        if (r->reproducible) {
-            // records instead of atomics: every slot starts empty (DET_NO_KEY = all ones)
-            TRY(ensure_det_buffers(r));
-            HIP_TRY(r, hipMemsetAsync(r->d_det_keys, 0xFF, (size_t)MAX_VERTS * B * sizeof(unsigned), st));
-            if (r->n_mats <= LDS_MAT_CAP) CL2_RESOLVE(2, true, true); else CL2_RESOLVE(2, false, true);      // the record stores need registers the 168 of three waves do not leave
-        } else {
-            // (more than LDS_MAT_CAP materials: the table stays in global memory and its addresses take the registers that three
-            // waves per SIMD do not leave -- two waves, no scratch)
-            if (r->n_mats <= LDS_MAT_CAP) CL2_RESOLVE(3, true, false); else CL2_RESOLVE(2, false, false);
+        {
+            if (r->reproducible) {
+                // records instead of atomics: every slot starts empty (DET_NO_KEY = all ones)
+                TRY(ensure_det_buffers(r));
+                HIP_TRY(r, hipMemsetAsync(r->d_det_keys, 0xFF, (size_t)MAX_VERTS * B * sizeof(unsigned), st));
+            }
+            // the material table goes to LDS when it fits LDS_MAT_CAP entries (the reference ships 8): connect_resolve.hpp
+            const bool mats_lds = r->n_mats <= LDS_MAT_CAP;
+            // Three waves per SIMD take the LDS table and atomics.  The record stores of the reproducible form need registers the 168 of
+            // three waves do not leave; with more than LDS_MAT_CAP materials the table stays in global memory and its addresses take the
+            // registers that three waves per SIMD do not leave -- two waves, no scratch.
+            const bool three_waves = mats_lds && !r->reproducible && !layered;
+            auto launch = [&](auto W) {
+                with_flags([&](auto ML, auto DET, auto MAPPED, auto STRAT, auto LAYERS) {
+                    constexpr bool wants_three = ML.value && !DET.value && !LAYERS.value;
+                    if constexpr (wants_three == (W.value == 3) && !(LAYERS.value && (MAPPED.value || STRAT.value)))
+                        hipLaunchKernelGGL((k_connect_resolve<W.value, ML.value, DET.value, MAPPED.value, STRAT.value, LAYERS.value>),
+                                           dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats, r->n_mats, r->d_tri_shade, r->cam_tris,
+                                           r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_agg, r->d_light_image, r->d_uni, r->d_stats,
+                                           r->debug_flags, r->d_det_keys, r->d_det_vals, map, (unsigned long long)r->strategy_mask, r->lcodes,
+                                           r->d_lay_agg, r->d_lay_light);
+                }, mats_lds, r->reproducible, map != nullptr, masked, layered);
+            };
+            if (three_waves) launch(int_c<3>{}); else launch(int_c<2>{});
         }
-#undef CL2_RESOLVE
-#undef CL2_RESOLVE_M
-#undef CL2_RESOLVE_L
-#undef CL2_RESOLVE_S
     }
     HIP_TRY(r, hipGetLastError());
     if (r->reproducible) {
@@ -798,20 +801,16 @@ int launch_finalize(cl2_renderer* r, hipStream_t st) {
 }
 
 // with error tracking on (r->d_mom allocated) the <true> forms also add every addend's second moments; with robust buckets on
-// (r->d_bkt allocated) the <., true> forms also add every addend to its bucket
-#define LAUNCH_ACCUMULATING(kernel, ...)                                                                                          \
-    do {                                                                                                                          \
-        if (r->d_bkt) {                                                                                                           \
-            if (r->d_mom) hipLaunchKernelGGL((kernel<true, true>), dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, __VA_ARGS__);       \
-            else hipLaunchKernelGGL((kernel<false, true>), dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, __VA_ARGS__);               \
-        } else if (r->d_mom) hipLaunchKernelGGL((kernel<true>), dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, __VA_ARGS__);          \
-        else hipLaunchKernelGGL((kernel<false>), dim3(grid_for(r->FB)), dim3(BLOCK), 0, st, __VA_ARGS__);                         \
-    } while (0)
+// (r->d_bkt allocated) the <., true> forms also add every addend to its bucket: f(MOMENTS, BUCKETS) launches the kernel
+template <class F> void launch_accumulating(cl2_renderer* r, F&& f) { with_flags(f, r->d_mom != nullptr, r->d_bkt != nullptr); }
 
 int launch_accumulate(cl2_renderer* r, hipStream_t st) {
     Timed t(r, ST_ACCUMULATE, st);
-    LAUNCH_ACCUMULATING(k_accumulate, r->FB, r->streams, r->d_finalized, r->d_sample_w, r->d_light_image, r->d_uni, r->d_acc, r->d_mom,
-                        r->d_bkt, r->bkt_M);
+    const dim3 grid(grid_for(r->FB)), block(BLOCK);
+    launch_accumulating(r, [&](auto MOM, auto BKT) {
+        hipLaunchKernelGGL((k_accumulate<MOM.value, BKT.value>), grid, block, 0, st, r->FB, r->streams, r->d_finalized, r->d_sample_w,
+                           r->d_light_image, r->d_uni, r->d_acc, r->d_mom, r->d_bkt, r->bkt_M);
+    });
     r->acc_clean = false;
     HIP_TRY(r, hipGetLastError());
     return launch_layers_accumulate(r, st);
@@ -820,12 +819,16 @@ int launch_accumulate(cl2_renderer* r, hipStream_t st) {
 // `mapped`: the pass ran with the density's slot maps, `pass` = its number (adaptive.hpp)
 int launch_finalize_accumulate(cl2_renderer* r, hipStream_t st, bool mapped = false, uint32_t pass = 0) {
     Timed t(r, ST_FINALIZE, st);
-    if (mapped)
-        LAUNCH_ACCUMULATING(k_finalize_accumulate_mapped, r->B, r->W, r->H, r->d_agg, r->d_light_image, r->d_uni, r->d_acc, r->d_mom,
-                            r->d_dens_C, r->d_dens_invm, pass, r->d_cam_count, r->d_bkt, r->bkt_M);
-    else
-        LAUNCH_ACCUMULATING(k_finalize_accumulate, r->B, r->W, r->H, r->d_agg, r->d_light_image, r->d_uni, r->d_acc, r->d_mom, r->d_bkt,
-                            r->bkt_M);
+    const dim3 grid(grid_for(r->FB)), block(BLOCK);
+    launch_accumulating(r, [&](auto MOM, auto BKT) {
+        if (mapped)
+            hipLaunchKernelGGL((k_finalize_accumulate_mapped<MOM.value, BKT.value>), grid, block, 0, st, r->B, r->W, r->H, r->d_agg,
+                               r->d_light_image, r->d_uni, r->d_acc, r->d_mom, r->d_dens_C, r->d_dens_invm, pass, r->d_cam_count, r->d_bkt,
+                               r->bkt_M);
+        else
+            hipLaunchKernelGGL((k_finalize_accumulate<MOM.value, BKT.value>), grid, block, 0, st, r->B, r->W, r->H, r->d_agg,
+                               r->d_light_image, r->d_uni, r->d_acc, r->d_mom, r->d_bkt, r->bkt_M);
+    });
     r->acc_clean = false;
     HIP_TRY(r, hipGetLastError());
     return launch_layers_accumulate(r, st);       // (never after a mapped pass: launch_resolve refuses a density while a table is set)
@@ -1382,39 +1385,68 @@ int cl2_read_accumulators(cl2_renderer* r, float* img, float* wts, int32_t* coun
     return CL2_OK;
 }
 
-int cl2_reset_accumulators(cl2_renderer* r) {
-    if (!r) return CL2_E_INVALID;
-    HIP_TRY(r, hipSetDevice(r->device));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipMemset(r->d_acc, 0, 8 * (size_t)r->FB * sizeof(float)));
-    if (r->d_mom) HIP_TRY(r, hipMemset(r->d_mom, 0, 8 * (size_t)r->FB * sizeof(float)));
-    if (r->d_bkt) HIP_TRY(r, hipMemset(r->d_bkt, 0, 4 * (size_t)r->bkt_M * (size_t)r->FB * sizeof(float)));
-    if (r->d_cam_count) HIP_TRY(r, hipMemset(r->d_cam_count, 0, (size_t)r->FB * sizeof(unsigned)));
-    r->cam_uniform = 0;
-    if (r->d_lacc) HIP_TRY(r, hipMemset(r->d_lacc, 0, 3 * (size_t)r->n_layers * (size_t)r->FB * sizeof(float)));
-    r->mom_valid = r->d_mom != nullptr;
-    r->bkt_valid = r->d_bkt != nullptr;
-    r->lay_valid = r->n_layers > 0;
-    r->acc_clean = true;
-    r->samples = 0;
+namespace {
+// The side sums of the accumulators: moments (error_estimate.hpp), buckets (robust.hpp) and layer accumulators (layers.hpp).  Each
+// is a float array that exists while its feature is on, and a flag: every addend in the accumulators also went into the side sum.
+// The rules of that flag, for all of them:
+//   switched on           valid if the accumulators hold nothing yet (side_sum_on)
+//   cl2_reset_accumulators  zeroed, and valid if present (reset_side_sums)
+//   accumulators written by the caller  invalid (invalidate_side_sums) until the matching cl2_write_*_packed brings the side sum
+struct SideSum { float*& p; size_t n_floats; bool& valid; };
+inline std::array<SideSum, 3> side_sums(cl2_renderer* r) {
+    const size_t FB = (size_t)r->FB;
+    return {{{r->d_mom, 8 * FB, r->mom_valid}, {r->d_bkt, 4 * (size_t)r->bkt_M * FB, r->bkt_valid}, {r->d_lacc, 3 * (size_t)r->n_layers * FB, r->lay_valid}}};
+}
+int reset_side_sums(cl2_renderer* r) {
+    for (SideSum& s : side_sums(r)) {
+        if (s.p) HIP_TRY(r, hipMemset(s.p, 0, s.n_floats * sizeof(float)));
+        s.valid = s.p != nullptr;
+    }
     return CL2_OK;
 }
-
-static int acc_copy(cl2_renderer* r, void* dst, const void* src, size_t n_floats, hipMemcpyKind kind) {
-    if (!r || !dst || !src) return CL2_E_INVALID;
-    if (n_floats != 8 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed accumulators hold 8*W*H floats");
+void invalidate_side_sums(cl2_renderer* r) {
+    for (SideSum& s : side_sums(r)) s.valid = false;
+}
+// allocates and zeroes a side sum of n floats; `what` names it in the error text
+int side_sum_on(cl2_renderer* r, float*& p, size_t n_floats, bool& valid, const char* what) {
+    TRY(dev_alloc(r, &p, n_floats));
+    if (hipMemset(p, 0, n_floats * sizeof(float)) != hipSuccess) return fail(r, CL2_E_HIP, std::string(what) + ": initialisation failed");
+    valid = r->acc_clean;                // samples rendered without it: invalid until cl2_reset_accumulators
+    return CL2_OK;
+}
+// what every read / write of packed accumulators or side sums ends in, after the entry point's own refusals
+int packed_copy(cl2_renderer* r, void* dst, const void* src, size_t n_floats, hipMemcpyKind kind) {
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
     HIP_TRY(r, hipMemcpy(dst, src, n_floats * sizeof(float), kind));
     return CL2_OK;
 }
-int cl2_read_accumulators_packed(cl2_renderer* r, float* dst, size_t n) { return acc_copy(r, dst, r ? r->d_acc : nullptr, n, hipMemcpyDeviceToHost); }
-int cl2_write_accumulators_packed(cl2_renderer* r, const float* src, size_t n) {
-    TRY(acc_copy(r, r ? r->d_acc : nullptr, src, n, hipMemcpyHostToDevice));
+}  // namespace
+
+int cl2_reset_accumulators(cl2_renderer* r) {
+    if (!r) return CL2_E_INVALID;
+    HIP_TRY(r, hipSetDevice(r->device));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipMemset(r->d_acc, 0, 8 * (size_t)r->FB * sizeof(float)));
+    if (r->d_cam_count) HIP_TRY(r, hipMemset(r->d_cam_count, 0, (size_t)r->FB * sizeof(unsigned)));
+    r->cam_uniform = 0;
+    TRY(reset_side_sums(r));
+    r->acc_clean = true;
+    r->samples = 0;
+    return CL2_OK;
+}
+
+int cl2_read_accumulators_packed(cl2_renderer* r, float* dst, size_t n_floats) {
+    if (!r || !dst) return CL2_E_INVALID;
+    if (n_floats != 8 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed accumulators hold 8*W*H floats");
+    return packed_copy(r, dst, r->d_acc, n_floats, hipMemcpyDeviceToHost);
+}
+int cl2_write_accumulators_packed(cl2_renderer* r, const float* src, size_t n_floats) {
+    if (!r || !src) return CL2_E_INVALID;
+    if (n_floats != 8 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed accumulators hold 8*W*H floats");
+    TRY(packed_copy(r, r->d_acc, src, n_floats, hipMemcpyHostToDevice));
     r->acc_clean = false;
-    r->mom_valid = false;                // until cl2_write_moments_packed brings the moments that go with these sums
-    r->bkt_valid = false;                // ... and cl2_write_buckets_packed the buckets
-    r->lay_valid = false;                // ... and cl2_write_layers_packed the layer accumulators
+    invalidate_side_sums(r);
     return CL2_OK;
 }
 
@@ -1936,13 +1968,10 @@ int cl2_set_layers(cl2_renderer* r, const uint64_t* masks, int n_layers) {
     lc.n_layers = n_layers;
     r->n_layers = n_layers;
     int rc = alloc_layer_entries(r);
-    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_lacc, 3 * (size_t)n_layers * (size_t)r->FB);
-    if (rc == CL2_OK && hipMemset(r->d_lacc, 0, 3 * (size_t)n_layers * (size_t)r->FB * sizeof(float)) != hipSuccess)
-        rc = fail(r, CL2_E_HIP, "layer accumulators: initialisation failed");
+    if (rc == CL2_OK) rc = side_sum_on(r, r->d_lacc, 3 * (size_t)n_layers * (size_t)r->FB, r->lay_valid, "layer accumulators");
     if (rc != CL2_OK) { const std::string why = r->err; free_layers(r); return fail(r, rc, why + " (layers are off)"); }
     std::copy(m, m + CL2_MAX_LAYERS, r->layer_masks);
     r->lcodes = lc;
-    r->lay_valid = r->acc_clean;         // samples rendered without this table: invalid until cl2_reset_accumulators
     return CL2_OK;
 }
 int cl2_get_layers(const cl2_renderer* r, uint64_t* masks_out, int capacity) {
@@ -1956,17 +1985,12 @@ int cl2_read_layers_packed(cl2_renderer* r, float* dst, size_t n_floats) {
     if (!r->lay_valid)
         return fail(r, CL2_E_STATE, "the layer accumulators do not cover every sample in the accumulators (the table was set or changed after "
                                     "samples, or accumulators were written without them): cl2_reset_accumulators or cl2_write_layers_packed");
-    HIP_TRY(r, hipSetDevice(r->device));
-    TRY(drain(r));
-    HIP_TRY(r, hipMemcpy(dst, r->d_lacc, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return CL2_OK;
+    return packed_copy(r, dst, r->d_lacc, n_floats, hipMemcpyDeviceToHost);
 }
 int cl2_write_layers_packed(cl2_renderer* r, const float* src, size_t n_floats) {
     if (!r || !src) return CL2_E_INVALID;
     TRY(need_layers(r, n_floats));
-    HIP_TRY(r, hipSetDevice(r->device));
-    TRY(drain(r));
-    HIP_TRY(r, hipMemcpy(r->d_lacc, src, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    TRY(packed_copy(r, r->d_lacc, src, n_floats, hipMemcpyHostToDevice));
     r->lay_valid = true;
     return CL2_OK;
 }
@@ -2050,37 +2074,34 @@ int cl2_reset_counters(cl2_renderer* r) {
 int cl2_export_rays(cl2_renderer* r, int which, void* out, size_t n_records) {
     STAGE_PROLOGUE(r);
     if (!out || (which != CL2_LIGHT && which != CL2_CAMERA) || n_records != (size_t)r->FB) return fail(r, CL2_E_INVALID, "bad export_rays arguments");
-    RayRec* d = nullptr;
-    TRY(dev_alloc(r, &d, (size_t)r->FB));
-    hipLaunchKernelGGL(k_export_rays, dim3(grid_for(r->FB)), dim3(BLOCK), 0, r->stream, r->FB, r->export_stream * r->FB, r->sets[r->cur][which], which == CL2_CAMERA ? 1 : 0, d);
-    int rc = drain(r);
-    if (rc == CL2_OK && hipMemcpy(out, d, (size_t)r->FB * sizeof(RayRec), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(r, CL2_E_HIP, "export copy failed");
-    dev_free(r, d);
-    return rc;
+    Scratch<RayRec> d(r);
+    TRY(d.alloc((size_t)r->FB));
+    hipLaunchKernelGGL(k_export_rays, dim3(grid_for(r->FB)), dim3(BLOCK), 0, r->stream, r->FB, r->export_stream * r->FB, r->sets[r->cur][which], which == CL2_CAMERA ? 1 : 0, d.p);
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(out, d, (size_t)r->FB * sizeof(RayRec), hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 int cl2_export_paths(cl2_renderer* r, int which, void* out, size_t n_records) {
     STAGE_PROLOGUE(r);
     if (!out || (which != CL2_LIGHT && which != CL2_CAMERA) || n_records != (size_t)r->FB) return fail(r, CL2_E_INVALID, "bad export_paths arguments");
-    unsigned char* d = nullptr;
-    TRY(dev_alloc(r, &d, (size_t)r->FB * 1040));
-    hipLaunchKernelGGL(k_export_paths, dim3(grid_for(r->FB)), dim3(BLOCK), 0, r->stream, r->FB, r->export_stream * r->FB, r->B, r->sets[r->cur][which], which == CL2_CAMERA ? 1 : 0, d);
-    int rc = drain(r);
-    if (rc == CL2_OK && hipMemcpy(out, d, (size_t)r->FB * 1040, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(r, CL2_E_HIP, "export copy failed");
-    dev_free(r, d);
-    return rc;
+    Scratch<unsigned char> d(r);
+    TRY(d.alloc((size_t)r->FB * 1040));
+    hipLaunchKernelGGL(k_export_paths, dim3(grid_for(r->FB)), dim3(BLOCK), 0, r->stream, r->FB, r->export_stream * r->FB, r->B, r->sets[r->cur][which], which == CL2_CAMERA ? 1 : 0, d.p);
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(out, d, (size_t)r->FB * 1040, hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 int cl2_export_aggregators(cl2_renderer* r, void* out, size_t n_records) {
     STAGE_PROLOGUE(r);
     if (!out || n_records != (size_t)r->FB) return fail(r, CL2_E_INVALID, "bad export_aggregators arguments");
-    float* d = nullptr;
-    TRY(dev_alloc(r, &d, (size_t)r->FB * 32));
-    hipLaunchKernelGGL(k_export_aggregators, dim3(grid_for(r->FB)), dim3(BLOCK), 0, r->stream, r->FB, r->export_stream * r->FB, r->B, r->d_agg, d);
-    int rc = drain(r);
-    if (rc == CL2_OK && hipMemcpy(out, d, (size_t)r->FB * 128, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(r, CL2_E_HIP, "export copy failed");
-    dev_free(r, d);
-    return rc;
+    Scratch<float> d(r);
+    TRY(d.alloc((size_t)r->FB * 32));
+    hipLaunchKernelGGL(k_export_aggregators, dim3(grid_for(r->FB)), dim3(BLOCK), 0, r->stream, r->FB, r->export_stream * r->FB, r->B, r->d_agg, d.p);
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(out, d, (size_t)r->FB * 128, hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 int cl2_export_connections(cl2_renderer* r, uint64_t* cmask, int32_t* tri, float* t1, size_t n_pixels) {
@@ -2119,53 +2140,74 @@ int cl2_import_sample_images(cl2_renderer* r, const float* fin4, const float* li
     return CL2_OK;
 }
 
-int cl2_probe_traverse(cl2_renderer* r, const void* rays_v, size_t n_rays, int32_t* best_i, float* best_t, float* u, float* v) {
-    STAGE_PROLOGUE(r);
-    if (!rays_v || !best_i || !best_t || !u || !v) return fail(r, CL2_E_INVALID, "NULL probe array");
-    if (n_rays == 0) return CL2_OK;
+namespace {
+// the device side of a probe call: origins, directions, hit records, seeded targets (cl2_probe_visibility only), the ray count
+struct ProbeRays {
+    Scratch<float4> o, d, h;
+    Scratch<int> t;
+    Scratch<unsigned> n;
+    explicit ProbeRays(cl2_renderer* r) : o(r), d(r), h(r), t(r), n(r) {}
+};
+
+// The front of both probe calls after their own checks: the ray count's bound, `target` (if any) checked against the scene, the
+// RayRec array as float4 origins and directions on the device, the count beside them; `wide`: the walk's work counter starts at 0.
+int probe_upload(cl2_renderer* r, const void* rays_v, size_t n_rays, const int32_t* target, bool wide, ProbeRays& p) {
     if (n_rays > (size_t)1 << 30) return fail(r, CL2_E_INVALID, "too many probe rays");
+    for (size_t i = 0; target && i < n_rays; i++)
+        if (target[i] >= r->bvh.n_tris) return fail(r, CL2_E_INVALID, "probe target is not a triangle of the scene");
     const RayRec* rays = static_cast<const RayRec*>(rays_v);
-    std::vector<float4> o(n_rays), d(n_rays), h(n_rays);
+    std::vector<float4> o(n_rays), d(n_rays);
     for (size_t i = 0; i < n_rays; i++) {
         o[i] = make_float4(rays[i].origin[0], rays[i].origin[1], rays[i].origin[2], 0.0f);
         d[i] = make_float4(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2], 0.0f);
     }
-    float4 *d_o = nullptr, *d_d = nullptr, *d_h = nullptr;
-    unsigned* d_n = nullptr;
-    int rc = dev_alloc(r, &d_o, n_rays);
-    if (rc == CL2_OK) rc = dev_alloc(r, &d_d, n_rays);
-    if (rc == CL2_OK) rc = dev_alloc(r, &d_h, n_rays);
-    if (rc == CL2_OK) rc = dev_alloc(r, &d_n, (size_t)1);
-    if (rc == CL2_OK) {
-        const unsigned n = (unsigned)n_rays;
-        bool ok = hipMemcpy(d_o, o.data(), n_rays * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(d_d, d.data(), n_rays * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(d_n, &n, sizeof n, hipMemcpyHostToDevice) == hipSuccess;
-        if (!ok) rc = fail(r, CL2_E_HIP, "probe upload failed");
+    TRY(p.o.alloc(n_rays));
+    TRY(p.d.alloc(n_rays));
+    TRY(p.h.alloc(n_rays));
+    if (target) TRY(p.t.alloc(n_rays));
+    TRY(p.n.alloc(1));
+    const unsigned n = (unsigned)n_rays;
+    HIP_TRY(r, hipMemcpy(p.o, o.data(), n_rays * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(r, hipMemcpy(p.d, d.data(), n_rays * sizeof(float4), hipMemcpyHostToDevice));
+    if (target) HIP_TRY(r, hipMemcpy(p.t, target, n_rays * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(r, hipMemcpy(p.n, &n, sizeof n, hipMemcpyHostToDevice));
+    if (wide) HIP_TRY(r, hipMemsetAsync(r->d_work, 0, WORK_STRIDE * sizeof(unsigned), r->stream));
+    return CL2_OK;
+}
+
+// ... and their end: the hit records of the finished launch, on the host
+int probe_read_back(cl2_renderer* r, const ProbeRays& p, size_t n_rays, std::vector<float4>& h) {
+    TRY(drain(r));
+    h.resize(n_rays);
+    HIP_TRY(r, hipMemcpy(h.data(), p.h, n_rays * sizeof(float4), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+}  // namespace
+
+int cl2_probe_traverse(cl2_renderer* r, const void* rays_v, size_t n_rays, int32_t* best_i, float* best_t, float* u, float* v) {
+    STAGE_PROLOGUE(r);
+    if (!rays_v || !best_i || !best_t || !u || !v) return fail(r, CL2_E_INVALID, "NULL probe array");
+    if (n_rays == 0) return CL2_OK;
+    // the probe through the exact 4-wide walk (rays with a non-finite 1/d take the binary walk inside it)
+    const bool wide = r->traversal_mode == 5 && r->n_wide > 0 && !count_ref(r);
+    ProbeRays p(r);
+    TRY(probe_upload(r, rays_v, n_rays, nullptr, wide, p));
+    if (wide) {
+        PathRaySource src{nullptr, p.o, p.d, p.h};
+        TRY(launch_wide(r, r->stream, 0, p.n, r->d_work, src, 0));
+    } else {
+        with_flags([&](auto CNT) {
+            hipLaunchKernelGGL(k_traverse_paths<CNT.value>, dim3(grid_for(n_rays)), dim3(BLOCK), bvh_lds_bytes(r), r->stream, r->bvh,
+                               (const int*)nullptr, p.n.p, p.o.p, p.d.p, p.h.p, r->d_stats);
+        }, count_ref(r));
     }
-    if (rc == CL2_OK && r->traversal_mode == 5 && r->n_wide > 0 && !count_ref(r)) {
-        // the probe through the exact 4-wide walk (rays with a non-finite 1/d take the binary walk inside it)
-        if (hipMemsetAsync(r->d_work, 0, WORK_STRIDE * sizeof(unsigned), r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "probe memset failed");
-        if (rc == CL2_OK) {
-            PathRaySource src{nullptr, d_o, d_d, d_h};
-            rc = launch_wide(r, r->stream, 0, d_n, r->d_work, src, 0);
-            if (rc == CL2_OK) rc = drain(r);
-        }
-    } else if (rc == CL2_OK) {
-        if (count_ref(r))
-            hipLaunchKernelGGL(k_traverse_paths<true>, dim3(grid_for(n_rays)), dim3(BLOCK), bvh_lds_bytes(r), r->stream, r->bvh, (const int*)nullptr, d_n, d_o, d_d, d_h, r->d_stats);
-        else
-            hipLaunchKernelGGL(k_traverse_paths<false>, dim3(grid_for(n_rays)), dim3(BLOCK), bvh_lds_bytes(r), r->stream, r->bvh, (const int*)nullptr, d_n, d_o, d_d, d_h, r->d_stats);
-        rc = drain(r);
+    std::vector<float4> h;
+    TRY(probe_read_back(r, p, n_rays, h));
+    for (size_t i = 0; i < n_rays; i++) {
+        std::memcpy(&best_i[i], &h[i].x, 4);
+        best_t[i] = h[i].y; u[i] = h[i].z; v[i] = h[i].w;
     }
-    if (rc == CL2_OK && hipMemcpy(h.data(), d_h, n_rays * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(r, CL2_E_HIP, "probe download failed");
-    if (rc == CL2_OK)
-        for (size_t i = 0; i < n_rays; i++) {
-            std::memcpy(&best_i[i], &h[i].x, 4);
-            best_t[i] = h[i].y; u[i] = h[i].z; v[i] = h[i].w;
-        }
-    dev_free(r, d_o); dev_free(r, d_d); dev_free(r, d_h); dev_free(r, d_n);
-    return rc;
+    return CL2_OK;
 }
 
 int cl2_probe_visibility(cl2_renderer* r, const void* rays_v, size_t n_rays, const int32_t* target, int32_t* out_tri, float* out_t) {
@@ -2174,45 +2216,17 @@ int cl2_probe_visibility(cl2_renderer* r, const void* rays_v, size_t n_rays, con
     if (r->n_wide <= 0) return fail(r, CL2_E_STATE, "the uploaded scene has no 4-wide collapse: no seeded walk");
     if ((r->debug_flags >> 13) & 1) return fail(r, CL2_E_STATE, "the seeded walk exists for the speculative walk only: clear debug bit 13");
     if (n_rays == 0) return CL2_OK;
-    if (n_rays > (size_t)1 << 30) return fail(r, CL2_E_INVALID, "too many probe rays");
-    for (size_t i = 0; i < n_rays; i++)
-        if (target[i] >= r->bvh.n_tris) return fail(r, CL2_E_INVALID, "probe target is not a triangle of the scene");
-    const RayRec* rays = static_cast<const RayRec*>(rays_v);
-    std::vector<float4> o(n_rays), d(n_rays), h(n_rays);
+    ProbeRays p(r);
+    TRY(probe_upload(r, rays_v, n_rays, target, true, p));
+    ProbeVisRaySource src{p.o, p.d, p.t, p.h};
+    TRY((launch_wide<ProbeVisRaySource, true>(r, r->stream, 0, p.n, r->d_work, src, 0)));
+    std::vector<float4> h;
+    TRY(probe_read_back(r, p, n_rays, h));
     for (size_t i = 0; i < n_rays; i++) {
-        o[i] = make_float4(rays[i].origin[0], rays[i].origin[1], rays[i].origin[2], 0.0f);
-        d[i] = make_float4(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2], 0.0f);
+        std::memcpy(&out_tri[i], &h[i].x, 4);
+        out_t[i] = h[i].y;
     }
-    float4 *d_o = nullptr, *d_d = nullptr, *d_h = nullptr;
-    int* d_t = nullptr;
-    unsigned* d_n = nullptr;
-    int rc = dev_alloc(r, &d_o, n_rays);
-    if (rc == CL2_OK) rc = dev_alloc(r, &d_d, n_rays);
-    if (rc == CL2_OK) rc = dev_alloc(r, &d_h, n_rays);
-    if (rc == CL2_OK) rc = dev_alloc(r, &d_t, n_rays);
-    if (rc == CL2_OK) rc = dev_alloc(r, &d_n, (size_t)1);
-    if (rc == CL2_OK) {
-        const unsigned n = (unsigned)n_rays;
-        bool ok = hipMemcpy(d_o, o.data(), n_rays * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(d_d, d.data(), n_rays * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(d_t, target, n_rays * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(d_n, &n, sizeof n, hipMemcpyHostToDevice) == hipSuccess;
-        if (!ok) rc = fail(r, CL2_E_HIP, "probe upload failed");
-    }
-    if (rc == CL2_OK && hipMemsetAsync(r->d_work, 0, WORK_STRIDE * sizeof(unsigned), r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "probe memset failed");
-    if (rc == CL2_OK) {
-        ProbeVisRaySource src{d_o, d_d, d_t, d_h};
-        rc = launch_wide<ProbeVisRaySource, true>(r, r->stream, 0, d_n, r->d_work, src, 0);
-        if (rc == CL2_OK) rc = drain(r);
-    }
-    if (rc == CL2_OK && hipMemcpy(h.data(), d_h, n_rays * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(r, CL2_E_HIP, "probe download failed");
-    if (rc == CL2_OK)
-        for (size_t i = 0; i < n_rays; i++) {
-            std::memcpy(&out_tri[i], &h[i].x, 4);
-            out_t[i] = h[i].y;
-        }
-    dev_free(r, d_o); dev_free(r, d_d); dev_free(r, d_h); dev_free(r, d_t); dev_free(r, d_n);
-    return rc;
+    return CL2_OK;
 }
 
 // ---- first-hit features and the denoiser (denoise.hpp) ----
@@ -2337,12 +2351,10 @@ int run_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
         const float4* cin = r->d_dn[i & 1];
         float4* cout = r->d_dn[(i + 1) & 1];
         float* out3 = i == iterations - 1 ? dst : nullptr;
-        if (step == 1)
-            hipLaunchKernelGGL(k_denoise_pass<1>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
-        else if (step == 2)
-            hipLaunchKernelGGL(k_denoise_pass<2>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
-        else
-            hipLaunchKernelGGL(k_denoise_pass<0>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
+        auto pass = [&](auto LDS_STEP) {
+            hipLaunchKernelGGL(k_denoise_pass<LDS_STEP.value>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
+        };
+        if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
         HIP_TRY(r, hipGetLastError());
     }
     return drain(r);
@@ -2481,10 +2493,7 @@ int cl2_set_error_tracking(cl2_renderer* r, int on) {
         return CL2_OK;
     }
     if (r->d_mom) return CL2_OK;
-    TRY(dev_alloc(r, &r->d_mom, 8 * (size_t)r->FB));
-    HIP_TRY(r, hipMemset(r->d_mom, 0, 8 * (size_t)r->FB * sizeof(float)));
-    r->mom_valid = r->acc_clean;
-    return CL2_OK;
+    return side_sum_on(r, r->d_mom, 8 * (size_t)r->FB, r->mom_valid, "moments");
 }
 
 int cl2_get_error_tracking(const cl2_renderer* r) { return r ? (r->d_mom ? 1 : 0) : CL2_E_INVALID; }
@@ -2493,19 +2502,14 @@ int cl2_read_moments_packed(cl2_renderer* r, float* dst, size_t n_floats) {
     if (!r || !dst) return CL2_E_INVALID;
     if (n_floats != 8 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed moments hold 8*W*H floats");
     TRY(need_moments(r));
-    HIP_TRY(r, hipSetDevice(r->device));
-    TRY(drain(r));
-    HIP_TRY(r, hipMemcpy(dst, r->d_mom, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return CL2_OK;
+    return packed_copy(r, dst, r->d_mom, n_floats, hipMemcpyDeviceToHost);
 }
 
 int cl2_write_moments_packed(cl2_renderer* r, const float* src, size_t n_floats) {
     if (!r || !src) return CL2_E_INVALID;
     if (n_floats != 8 * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed moments hold 8*W*H floats");
     if (!r->d_mom) return fail(r, CL2_E_STATE, "error tracking is off (cl2_set_error_tracking)");
-    HIP_TRY(r, hipSetDevice(r->device));
-    TRY(drain(r));
-    HIP_TRY(r, hipMemcpy(r->d_mom, src, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    TRY(packed_copy(r, r->d_mom, src, n_floats, hipMemcpyHostToDevice));
     r->mom_valid = true;
     return CL2_OK;
 }
@@ -2516,16 +2520,14 @@ int cl2_read_standard_error(cl2_renderer* r, float* out, size_t n_floats) {
     TRY(need_moments(r));
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
-    float4* d = nullptr;
-    HIP_TRY(r, hipMalloc(&d, (size_t)r->FB * sizeof(float4)));
+    Scratch<float4> d(r);
+    TRY(d.alloc((size_t)r->FB));
     hipLaunchKernelGGL(k_standard_error, dim3((r->FB + 255) / 256), dim3(256), 0, r->stream, r->FB, (const float*)r->d_acc,
-                       (const float*)r->d_mom, d);
-    int rc = hipGetLastError() == hipSuccess ? CL2_OK : fail(r, CL2_E_HIP, "k_standard_error launch failed");
-    if (rc == CL2_OK && hipStreamSynchronize(r->stream) != hipSuccess) rc = fail(r, CL2_E_HIP, "k_standard_error failed");
-    if (rc == CL2_OK && hipMemcpy(out, d, n_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(r, CL2_E_HIP, "standard error download failed");
-    (void)hipFree(d);
-    return rc;
+                       (const float*)r->d_mom, d.p);
+    HIP_TRY(r, hipGetLastError());
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipMemcpy(out, d, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 // ---------------------------------------------------------------- robust picture (csrc/robust.hpp)
@@ -2539,11 +2541,8 @@ int cl2_set_robust_buckets(cl2_renderer* r, int M) {
     r->bkt_M = 0;
     r->bkt_valid = false;
     if (M == 0) return CL2_OK;
-    const size_t n = 4 * (size_t)M * (size_t)r->FB;
-    TRY(dev_alloc(r, &r->d_bkt, n));
-    HIP_TRY(r, hipMemset(r->d_bkt, 0, n * sizeof(float)));
+    TRY(side_sum_on(r, r->d_bkt, 4 * (size_t)M * (size_t)r->FB, r->bkt_valid, "robust buckets"));
     r->bkt_M = M;
-    r->bkt_valid = r->acc_clean;
     return CL2_OK;
 }
 
@@ -2553,19 +2552,14 @@ int cl2_read_buckets_packed(cl2_renderer* r, float* dst, size_t n_floats) {
     if (!r || !dst) return CL2_E_INVALID;
     if (!r->d_bkt) return fail(r, CL2_E_STATE, "the robust buckets are off (cl2_set_robust_buckets)");
     if (n_floats != 4 * (size_t)r->bkt_M * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed buckets hold 4*M*W*H floats");
-    HIP_TRY(r, hipSetDevice(r->device));
-    TRY(drain(r));
-    HIP_TRY(r, hipMemcpy(dst, r->d_bkt, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return CL2_OK;
+    return packed_copy(r, dst, r->d_bkt, n_floats, hipMemcpyDeviceToHost);
 }
 
 int cl2_write_buckets_packed(cl2_renderer* r, const float* src, size_t n_floats) {
     if (!r || !src) return CL2_E_INVALID;
     if (!r->d_bkt) return fail(r, CL2_E_STATE, "the robust buckets are off (cl2_set_robust_buckets)");
     if (n_floats != 4 * (size_t)r->bkt_M * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed buckets hold 4*M*W*H floats");
-    HIP_TRY(r, hipSetDevice(r->device));
-    TRY(drain(r));
-    HIP_TRY(r, hipMemcpy(r->d_bkt, src, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    TRY(packed_copy(r, r->d_bkt, src, n_floats, hipMemcpyHostToDevice));
     r->bkt_valid = true;
     return CL2_OK;
 }
@@ -2602,16 +2596,13 @@ int cl2_robust_picture(cl2_renderer* r, float* out_bgr, size_t n_floats, float* 
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
     const size_t FB = (size_t)r->FB;
-    float* d = nullptr;
-    HIP_TRY(r, hipMalloc(&d, (5 * FB + 1) * sizeof(float)));
-    float2* d_stats = out_stats ? reinterpret_cast<float2*>(d + 3 * FB + (FB & 1)) : nullptr;   // 8-byte aligned: 3 FB + (FB & 1) is even
-    int rc = run_robust(r, d, d_stats);
-    if (rc == CL2_OK && hipMemcpy(out_bgr, d, n_floats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(r, CL2_E_HIP, "robust picture download failed");
-    if (rc == CL2_OK && out_stats && hipMemcpy(out_stats, d_stats, n_stats * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(r, CL2_E_HIP, "robust statistics download failed");
-    (void)hipFree(d);
-    return rc;
+    Scratch<float> d(r);
+    TRY(d.alloc(5 * FB + 1));
+    float2* d_stats = out_stats ? reinterpret_cast<float2*>(d.p + 3 * FB + (FB & 1)) : nullptr;   // 8-byte aligned: 3 FB + (FB & 1) is even
+    TRY(run_robust(r, d, d_stats));
+    HIP_TRY(r, hipMemcpy(out_bgr, d, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_stats) HIP_TRY(r, hipMemcpy(out_stats, d_stats, n_stats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 // The variance-guided filter (denoise_guided.hpp): cl2_denoise's passes with the luma edge-stop driven by the moments.
@@ -2650,12 +2641,10 @@ int run_guided(cl2_renderer* r, bool robust, int iterations, float sigma_luma, f
         const float4* cin = r->d_dn[i & 1];
         float4* cout = r->d_dn[(i + 1) & 1];
         float* out3 = i == iterations - 1 ? dst : nullptr;
-        if (step == 1)
-            hipLaunchKernelGGL(k_denoise_guided_pass<1>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
-        else if (step == 2)
-            hipLaunchKernelGGL(k_denoise_guided_pass<2>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
-        else
-            hipLaunchKernelGGL(k_denoise_guided_pass<0>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        auto pass = [&](auto LDS_STEP) {
+            hipLaunchKernelGGL(k_denoise_guided_pass<LDS_STEP.value>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        };
+        if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
         HIP_TRY(r, hipGetLastError());
     }
     return drain(r);
