@@ -99,6 +99,7 @@ EXPORTS = [
     "cl2_set_connection_query", "cl2_get_connection_query", "cl2_connection_query_active", "cl2_probe_visibility",
     "cl2_set_strategy_mask", "cl2_get_strategy_mask",
     "cl2_set_layers", "cl2_get_layers", "cl2_read_layers_packed", "cl2_write_layers_packed",
+    "cl2_denoise_layers", "cl2_keep_layer_picture",
 ]
 
 
@@ -169,6 +170,9 @@ def lib(variant=None):
         L.cl2_get_layers.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
         L.cl2_read_layers_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.cl2_write_layers_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_denoise_layers.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_size_t]
+        L.cl2_keep_layer_picture.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float]
         L.cl2_set_export_stream.argtypes = [C.c_void_p, C.c_int]
         L.cl2_comm_info.argtypes = [C.c_void_p, C.POINTER(CommInfo)]
         L.cl2_tone_log_sum.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]

@@ -24,6 +24,7 @@
 #include "kernels.hpp"
 #include "denoise.hpp"
 #include "denoise_guided.hpp"
+#include "denoise_layers.hpp"
 #include "denoise_robust.hpp"
 #include "error_estimate.hpp"
 #include "adaptive.hpp"
@@ -117,6 +118,7 @@ struct cl2_renderer {
     float4* d_lay_light = nullptr;
     float* d_lacc = nullptr;
     bool lay_valid = false;              // every sample in the accumulators was rendered under this table (the rules of mom_valid)
+    float4* d_ldn[2] = {nullptr, nullptr};   // the layers' filter (cl2_denoise_layers, denoise_layers.hpp): ping-pong [L][W*H], made on first use
     unsigned *d_det_keys = nullptr, *d_det_keys_sorted = nullptr, *d_det_slots = nullptr, *d_det_slots_sorted = nullptr;
     float4* d_det_vals = nullptr;
     void* d_det_tmp = nullptr;
@@ -130,7 +132,7 @@ struct cl2_renderer {
     double* d_tone_partial = nullptr;  // device tone map: per-workgroup partial sums + the total (allocated by the first call)
     uint8_t* d_tone_out = nullptr;     // device tone map: the uint8 picture before it is copied out
     float* d_pic = nullptr;            // kept picture (cl2_keep_picture, tonemap_picture.hpp): (H, W, 3) b, g, r, allocated on first use
-    int pic_kind = 0;                  // ... 0 none, 1 denoised, 2 guided, 3 robust, 4 robust-guided, 5 loaded (cl2_write_picture)
+    int pic_kind = 0;                  // ... 0 none, 1 denoised, 2 guided, 3 robust, 4 robust-guided, 5 loaded (cl2_write_picture), 6 layer, 7 sum of layers (cl2_keep_layer_picture)
     Stats* d_stats = nullptr;
     unsigned long long* d_block_stats = nullptr;   // [grid][4]: rays, box tests, tri tests, counted rays per workgroup slot
 
@@ -1923,6 +1925,7 @@ int cl2_get_strategy_mask(const cl2_renderer* r, uint64_t* mask_out) {
 namespace {
 void free_layers(cl2_renderer* r) {
     dev_free(r, r->d_lay_agg); dev_free(r, r->d_lay_light); dev_free(r, r->d_lacc);
+    dev_free(r, r->d_ldn[0]); dev_free(r, r->d_ldn[1]);
     r->n_layers = 0;
     r->lcodes = LayerCodes{};
     r->lay_valid = false;
@@ -1930,6 +1933,13 @@ void free_layers(cl2_renderer* r) {
 int need_layers(cl2_renderer* r, size_t n_floats) {
     if (r->n_layers == 0) return fail(r, CL2_E_STATE, "no layer table is set (cl2_set_layers)");
     if (n_floats != 3 * (size_t)r->n_layers * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed layer accumulators hold n_layers*3*W*H floats");
+    return CL2_OK;
+}
+// what reading lacc needs beyond a table (cl2_read_layers_packed, cl2_denoise_layers)
+int need_valid_layers(cl2_renderer* r) {
+    if (!r->lay_valid)
+        return fail(r, CL2_E_STATE, "the layer accumulators do not cover every sample in the accumulators (the table was set or changed after "
+                                    "samples, or accumulators were written without them): cl2_reset_accumulators or cl2_write_layers_packed");
     return CL2_OK;
 }
 }  // namespace
@@ -1982,9 +1992,7 @@ int cl2_get_layers(const cl2_renderer* r, uint64_t* masks_out, int capacity) {
 int cl2_read_layers_packed(cl2_renderer* r, float* dst, size_t n_floats) {
     if (!r || !dst) return CL2_E_INVALID;
     TRY(need_layers(r, n_floats));
-    if (!r->lay_valid)
-        return fail(r, CL2_E_STATE, "the layer accumulators do not cover every sample in the accumulators (the table was set or changed after "
-                                    "samples, or accumulators were written without them): cl2_reset_accumulators or cl2_write_layers_packed");
+    TRY(need_valid_layers(r));
     return packed_copy(r, dst, r->d_lacc, n_floats, hipMemcpyDeviceToHost);
 }
 int cl2_write_layers_packed(cl2_renderer* r, const float* src, size_t n_floats) {
@@ -2713,6 +2721,106 @@ int cl2_keep_picture(cl2_renderer* r, int kind, int iterations, float sigma, flo
 }
 
 int cl2_kept_picture(const cl2_renderer* r) { return r ? r->pic_kind : 0; }
+
+// ---------------------------------------------------------------- the filter over the layers (csrc/denoise_layers.hpp)
+namespace {
+int need_layer_filter_buffers(cl2_renderer* r) {
+    if (r->d_ldn[1]) return CL2_OK;
+    const size_t n = (size_t)r->n_layers * (size_t)r->FB;
+    int rc = dev_alloc(r, &r->d_ldn[0], n);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_ldn[1], n);          // last: its presence says the pair is complete
+    if (rc != CL2_OK) dev_free(r, r->d_ldn[0]);
+    return rc;
+}
+
+// cl2_denoise_layers and cl2_keep_layer_picture after their own argument checks (a table is set, sigma_color is not NULL): the
+// checks of run_denoise for every layer's sigma, the state checks, and every launch on drained streams.
+//   layer >= 0   only that layer is filtered; the last launch writes its (H, W, 3) picture to `dst` (device memory)
+//   layer == -1  every layer; the packed pictures [L][H][W][3] end in one working buffer (*layers_out) and, if `want_sum`, their sum
+//                goes to `dst`, or with dst == nullptr into the other working buffer (*sum_out)
+// Every refusal comes before the first launch.
+int run_denoise_layers(cl2_renderer* r, int layer, int iterations, const float* sigma_color, float sigma_depth, float sigma_albedo,
+                       bool want_sum, float* dst, const float** layers_out, const float** sum_out) {
+    const int L = r->n_layers;
+    if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
+    auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
+    if (bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
+    for (int l = 0; l < L; l++)
+        if (bad(sigma_color[l])) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
+    if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
+    for (int l = 0; l < L; l++)
+        if (iterations >= 1 && std::ldexp(sigma_color[l] * sigma_color[l], -2 * (iterations - 1)) < FLT_MIN)
+            return fail(r, CL2_E_INVALID, "sigma_color^2 * 4^-(iterations-1) underflows float32");
+    TRY(need_valid_layers(r));
+    if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
+    TRY(need_layer_filter_buffers(r));
+    const size_t FB = (size_t)r->FB;
+    const int l0 = layer < 0 ? 0 : layer, nl = layer < 0 ? L : 1;
+    float* const packed = layer < 0 ? (float*)r->d_ldn[iterations & 1] : dst;      // [nl][H][W][3], written by the last launch
+    hipStream_t st = r->stream;
+    hipLaunchKernelGGL(k_layers_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, l0, nl, (const float*)r->d_acc,
+                       (const float*)r->d_lacc, r->d_ldn[0], iterations == 0 ? packed : (float*)nullptr);
+    HIP_TRY(r, hipGetLastError());
+    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
+    const float den_a = sigma_albedo * sigma_albedo;
+    for (int i = 0; i < iterations; i++) {
+        const int step = 1 << i;
+        LayerDen den{};
+        for (int l = 0; l < L; l++) den.den_c[l] = std::ldexp(sigma_color[l] * sigma_color[l], -2 * i);      // as run_denoise
+        const float4* cin = r->d_ldn[i & 1];
+        float4* cout = r->d_ldn[(i + 1) & 1];
+        float* out3 = i == iterations - 1 ? packed : nullptr;
+        auto pass = [&](auto LDS_STEP) {
+            hipLaunchKernelGGL(k_layers_denoise_pass<LDS_STEP.value>, grid, block, 0, st, r->W, r->H, step, l0, nl, den, sigma_depth, den_a, cin,
+                               r->d_g0, r->d_g1, cout, out3);
+        };
+        if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
+        HIP_TRY(r, hipGetLastError());
+    }
+    if (layers_out) *layers_out = packed;
+    if (layer < 0 && want_sum) {
+        // the packed pictures fill 3/4 of their buffer; the other buffer was last read by the launch that wrote them
+        float* sum = dst ? dst : (float*)r->d_ldn[(iterations + 1) & 1];
+        hipLaunchKernelGGL(k_layers_sum, dim3(grid_for(3 * FB)), dim3(BLOCK), 0, st, 3 * FB, L, (const float*)packed, sum);
+        HIP_TRY(r, hipGetLastError());
+        if (sum_out) *sum_out = sum;
+    }
+    return drain(r);
+}
+}  // namespace
+
+int cl2_denoise_layers(cl2_renderer* r, int iterations, const float* sigma_color, float sigma_depth, float sigma_albedo,
+                       float* out_layers, size_t n_layer_floats, float* out_sum, size_t n_sum_floats) {
+    STAGE_PROLOGUE(r);
+    if (!sigma_color) return fail(r, CL2_E_INVALID, "NULL sigma_color (one per layer)");
+    if (!out_layers && !out_sum) return fail(r, CL2_E_INVALID, "NULL outputs: out_layers, out_sum or both");
+    if (r->n_layers == 0) return fail(r, CL2_E_STATE, "no layer table is set (cl2_set_layers)");
+    const size_t FB = (size_t)r->FB;
+    if (out_layers && n_layer_floats != 3 * (size_t)r->n_layers * FB) return fail(r, CL2_E_INVALID, "denoised layers must hold n_layers*3*W*H floats");
+    if (out_sum && n_sum_floats != 3 * FB) return fail(r, CL2_E_INVALID, "the sum of the denoised layers must hold 3*W*H floats");
+    TRY(drain(r));
+    const float *layers = nullptr, *sum = nullptr;
+    TRY(run_denoise_layers(r, -1, iterations, sigma_color, sigma_depth, sigma_albedo, out_sum != nullptr, nullptr, &layers, &sum));
+    if (out_layers) HIP_TRY(r, hipMemcpy(out_layers, layers, n_layer_floats * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_sum) HIP_TRY(r, hipMemcpy(out_sum, sum, n_sum_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
+}
+
+int cl2_keep_layer_picture(cl2_renderer* r, int layer, int iterations, const float* sigma_color, float sigma_depth, float sigma_albedo) {
+    STAGE_PROLOGUE(r);
+    if (!sigma_color) return fail(r, CL2_E_INVALID, "NULL sigma_color (one per layer)");
+    if (r->n_layers == 0) return fail(r, CL2_E_STATE, "no layer table is set (cl2_set_layers)");
+    if (layer < -1 || layer >= r->n_layers) return fail(r, CL2_E_INVALID, "kept layer picture: a layer of the table (0..n_layers-1) or -1 for the sum");
+    TRY(drain(r));
+    const bool fresh = !r->d_pic;
+    if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
+    const int rc = run_denoise_layers(r, layer, iterations, sigma_color, sigma_depth, sigma_albedo, true, r->d_pic, nullptr, nullptr);
+    if (rc == CL2_OK) r->pic_kind = layer < 0 ? 7 : 6;
+    else if (rc == CL2_E_HIP) r->pic_kind = 0;                    // launches may have written part of it
+    // every other refusal comes before the first launch: the previous picture stands; a buffer made for this call goes again
+    if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);
+    return rc;
+}
 
 int cl2_write_picture(cl2_renderer* r, const float* bgr, size_t n_floats) {
     if (!r || !bgr) return CL2_E_INVALID;

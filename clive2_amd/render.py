@@ -9,6 +9,7 @@ instead of opening a cv2 window (display code is out of scope).
     python -m clive2_amd.render --scene empty --samples 256 --robust-denoise --out cornell_robust_denoised.png
     python -m clive2_amd.render --scene empty --samples 64 --path-length 3: --out cornell_indirect_only.png
     python -m clive2_amd.render --scene empty --samples 64 --layers cornell
+    python -m clive2_amd.render --scene empty --samples 4 --layers cornell --single-pass --denoise-layers
 
 Several GPUs: start one process per GPU with RANK / LOCAL_RANK / WORLD_SIZE in the environment (e.g.
 `python -m torch.distributed.run --nproc-per-node N -m clive2_amd.render ...`; any spawner will do, torch
@@ -53,6 +54,32 @@ def _write_layers(renderer, args, K):
     for name, pic in layers.items():
         _save(f"{args.layers}_{name}.png", tone_map(pic, exposure=4.0, Lw=Lw))
     np.savez(f"{args.layers}_layers.npz", **layers)
+    return 0
+
+
+def _write_denoised_layers(renderer, args, K):
+    """--layers --single-pass --denoise-layers: one render with per-layer accumulators, the features, then every layer through the
+    filter on the device (Renderer.denoised_layers).  The pictures are tone-mapped ON THE DEVICE with the log-average of the
+    filtered SUM: keep the sum, picture_log_sum, then each layer with that Lw."""
+    t0 = time.time()
+    try:
+        renderer.reset_accumulators()
+        renderer.set_layers(strategies.LAYERS)
+        renderer.run_samples(-(-args.samples // K))
+        renderer.render_features(args.feature_samples)
+        layers, total = renderer.denoised_layers()
+        renderer.keep_layer_picture(None)
+        Lw = np.exp(np.float64(renderer.picture_log_sum()) / (args.width * args.height))
+        images = {"denoised": renderer.tone_mapped_picture(exposure=4.0, log_average=Lw)}
+        for name in layers:
+            renderer.keep_layer_picture(name)
+            images[name] = renderer.tone_mapped_picture(exposure=4.0, log_average=Lw)
+    finally:
+        renderer.close()
+    print(f"[rank 0] rendering and filtering {len(layers)} layers took {time.time() - t0:.2f} seconds")
+    for name, image in images.items():
+        _save(f"{args.layers}_{name}.png", image)
+    np.savez(f"{args.layers}_layers.npz", denoised=total, **layers)
     return 0
 
 
@@ -122,6 +149,10 @@ def main(argv=None):
     ap.add_argument("--single-pass", action="store_true",
                     help="with --layers: write the same pictures from ONE render with per-layer accumulators "
                          "(Renderer.render_layers_once, DESIGN.md 6.12) instead of one render per layer")
+    ap.add_argument("--denoise-layers", action="store_true",
+                    help="with --layers PREFIX --single-pass: render the first-hit features (--feature-samples), filter every layer on "
+                         "the device (Renderer.denoised_layers, DESIGN.md 6.14) and write the filtered PREFIX_<layer>.png, their sum "
+                         "PREFIX_denoised.png, all tone-mapped on the device with the log-average of the sum, and PREFIX_layers.npz")
     args = ap.parse_args(argv)
     # refused before any renderer is made
     if args.target_error is not None and not (args.target_error > 0 and np.isfinite(args.target_error)):
@@ -157,6 +188,8 @@ def main(argv=None):
         ap.error(str(e))
     if args.single_pass and args.layers is None:
         ap.error("--single-pass is a way to render --layers: give --layers PREFIX")
+    if args.denoise_layers and not (args.layers is not None and args.single_pass):
+        ap.error("--denoise-layers filters the layers of one render: give --layers PREFIX --single-pass")
     if args.layers is not None:
         if strategy_mask is not None:
             ap.error("--layers sets the strategy mask of each layer itself: it does not go with --strategies or --path-length")
@@ -194,6 +227,8 @@ def main(argv=None):
         renderer.set_strategy_mask(strategy_mask)      # before the first sample, the same on every rank
     # seed buffers of the job: stream k of rank r is buffer r * K + k
     renderer.set_seeds(stream_seeds(args.width * args.height, K, first_rank=rank * K))
+    if args.denoise_layers:
+        return _write_denoised_layers(renderer, args, K)
     if args.layers is not None:
         return _write_layers(renderer, args, K)
     if world > 1:

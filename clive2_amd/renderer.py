@@ -274,7 +274,7 @@ class Renderer:
 
     # ---- a kept picture and its tone map on the device (cl2_keep_picture ... cl2_picture_tone_map, csrc/tonemap_picture.hpp) ----
     _KEPT_KINDS = {"denoised": 1, "guided": 2, "robust": 3, "robust_guided": 4}
-    _KEPT_NAMES = {0: None, 1: "denoised", 2: "guided", 3: "robust", 4: "robust_guided", 5: "loaded"}
+    _KEPT_NAMES = {0: None, 1: "denoised", 2: "guided", 3: "robust", 4: "robust_guided", 5: "loaded", 6: "layer", 7: "layer_sum"}
 
     @staticmethod
     def _numpy2(what):
@@ -308,7 +308,8 @@ class Renderer:
 
     @property
     def kept_kind(self):
-        """what the handle keeps: None, "denoised", "guided", "robust", "robust_guided" or "loaded" (load_picture)"""
+        """what the handle keeps: None, "denoised", "guided", "robust", "robust_guided", "loaded" (load_picture), "layer" or "layer_sum"
+        (keep_layer_picture)"""
         return self._KEPT_NAMES[int(self._L.cl2_kept_picture(self._h))]
 
     def kept_picture(self):
@@ -577,6 +578,58 @@ class Renderer:
             with np.errstate(divide="ignore", invalid="ignore"):
                 out[name] = np.nan_to_num(img / wts, neginf=0, posinf=0)
         return out
+
+    # ---- the filter over the layers (cl2_denoise_layers, cl2_keep_layer_picture, csrc/denoise_layers.hpp) ----
+    # DENOISE_DEFAULTS, and a colour sigma per layer name where one measured better (a name not listed takes DENOISE_DEFAULTS'):
+    # on the 256 x 192, 4-pass set-up of DESIGN 6.3 the indirect layer of strategies.LAYERS wants a wide edge-stop (relative MSE of
+    # the sum on the glass scene 0.78 of the same-sigma sum's, Cornell box unchanged); emission and direct moved neither scene by
+    # more than 0.5 % anywhere between 0.5 and 32 (tools/layers_denoise_quality.py)
+    LAYER_DENOISE_DEFAULTS = dict(iterations=3, sigma_color={"indirect": 8.0}, sigma_depth=0.1, sigma_albedo=0.1)
+
+    def _layer_filter_args(self, iterations, sigma_color, sigma_depth, sigma_albedo):
+        d = self.LAYER_DENOISE_DEFAULTS
+        names = list(self.layers())
+        default = self.DENOISE_DEFAULTS["sigma_color"]
+        sc = {} if sigma_color is None else sigma_color
+        if isinstance(sc, dict):
+            unknown = sorted(set(sc) - set(names))
+            if unknown:
+                raise ValueError(f"sigma_color names layers that are not set: {unknown} (set: {names})")
+            sig = [float(sc.get(n, d["sigma_color"].get(n, default))) for n in names]
+        else:
+            sig = [float(sc)] * len(names)
+        arr = np.asarray(sig if sig else [default], dtype=np.float32)       # never NULL: without a table the library refuses
+        it = d["iterations"] if iterations is None else int(iterations)
+        sd = d["sigma_depth"] if sigma_depth is None else float(sigma_depth)
+        sa = d["sigma_albedo"] if sigma_albedo is None else float(sigma_albedo)
+        return names, it, arr, sd, sa
+
+    def denoised_layers(self, iterations=None, sigma_color=None, sigma_depth=None, sigma_albedo=None):
+        """The layers of the render in the accumulators (set_layers), each through the filter of denoised_radiance() with its
+        own colour sigma, and their sum, in ONE device call: ({name: (H,W,3) float32, BGR}, sum).  `sigma_color` is a float for
+        all layers or {name: float}; names not given take LAYER_DENOISE_DEFAULTS' value for that name, else
+        DENOISE_DEFAULTS'; the other unset arguments take LAYER_DENOISE_DEFAULTS.  Layer `name` is, byte for byte, denoised_radiance() of a render masked with that layer; the sum is
+        added in float32 in table order.  iterations=0 is layer_radiance() computed on the device.  render_features() first."""
+        names, it, sig, sd, sa = self._layer_filter_args(iterations, sigma_color, sigma_depth, sigma_albedo)
+        H, W = self.pixel_height, self.pixel_width
+        lay, tot = np.empty((max(len(names), 1), H, W, 3), np.float32), np.empty((H, W, 3), np.float32)
+        self._check(self._L.cl2_denoise_layers(self._h, it, ptr(sig), sd, sa, ptr(lay), C.c_size_t(len(names) * H * W * 3), ptr(tot),
+                                               C.c_size_t(tot.size)), "cl2_denoise_layers")
+        return {name: lay[l] for l, name in enumerate(names)}, tot
+
+    def keep_layer_picture(self, name=None, **params):
+        """Filter as denoised_layers(**params) does and KEEP one layer's picture (`name`) or the sum (None) in device memory, for
+        kept_picture(), picture_log_sum() and tone_mapped_picture(): the bytes of denoised_layers, nothing copied to the host.  For
+        a single layer only that layer is filtered.  keep_picture(None) drops it; a refused call leaves the previous kept picture."""
+        unknown = sorted(set(params) - {"iterations", "sigma_color", "sigma_depth", "sigma_albedo"})
+        if unknown:
+            raise TypeError(f"keep_layer_picture takes iterations, sigma_color, sigma_depth, sigma_albedo, not {unknown}")
+        names, it, sig, sd, sa = self._layer_filter_args(params.get("iterations"), params.get("sigma_color"),
+                                                         params.get("sigma_depth"), params.get("sigma_albedo"))
+        if name is not None and name not in names:
+            raise ValueError(f"keep_layer_picture: {name!r} is not a layer of the table (set: {names})")
+        layer = -1 if name is None else names.index(name)
+        self._check(self._L.cl2_keep_layer_picture(self._h, layer, it, ptr(sig), sd, sa), "cl2_keep_layer_picture")
 
     def render_layers_once(self, passes, layers=strategies.LAYERS, seeds=None):
         """The dictionary render_layers returns, from ONE render: reset_accumulators(), set_seeds(seeds), set_layers(layers),

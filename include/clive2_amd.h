@@ -586,6 +586,7 @@ int cl2_denoise_robust(cl2_renderer* r, int iterations, float sigma_luma, float 
  * The handle can keep ONE picture in device memory: (H, W, 3) float32 b, g, r, 12*W*H bytes, allocated on first use.  Its kind:
  *     0 none   1 denoised (cl2_denoise)   2 guided (cl2_denoise_guided)   3 robust (cl2_robust_picture)
  *     4 robust-guided (cl2_denoise_robust)   5 loaded (cl2_write_picture)
+ *     6 one filtered layer, 7 the sum of the filtered layers (cl2_keep_layer_picture, below: cl2_keep_picture makes neither)
  * It is a snapshot: it holds until it is replaced, dropped (kind 0) or the handle is destroyed; later samples, resets and scene
  * uploads do not change it.
  *
@@ -668,13 +669,41 @@ int cl2_get_strategy_mask(const cl2_renderer* r, uint64_t* mask_out);
  * reproducible switch, sample streams, every traversal organisation, pipelining and the visibility-query walk combine with a table
  * and describe the full picture as before.
  * OUT OF SCOPE: cl2_reduce_accumulators neither reduces nor refuses the layer accumulators -- a multi-rank host sums
- * cl2_read_layers_packed itself (every rank must set the same table).  There are no per-layer moments, buckets or denoisers and no
- * device tone map of layer pictures.  No reference counterpart (src/trace.metal:649-825 sums all pairs). */
+ * cl2_read_layers_packed itself (every rank must set the same table).  There are no per-layer moments or buckets.  The layers
+ * have a filter and, through the kept picture, a device tone map of their own: cl2_denoise_layers and cl2_keep_layer_picture below.
+ * No reference counterpart (src/trace.metal:649-825 sums all pairs). */
 #define CL2_MAX_LAYERS 8
 int cl2_set_layers(cl2_renderer* r, const uint64_t* masks, int n_layers);          /* NULL / 0 = off (the default) */
 int cl2_get_layers(const cl2_renderer* r, uint64_t* masks_out, int capacity);      /* returns n_layers */
 int cl2_read_layers_packed(cl2_renderer* r, float* host_dst, size_t n_floats);     /* [L][3][W*H], b g r */
 int cl2_write_layers_packed(cl2_renderer* r, const float* host_src, size_t n_floats);
+
+/* ---- the filter over the layers of one render (csrc/denoise_layers.hpp) ----
+ * cl2_denoise_layers filters every layer of the table in one call and adds the results.  Layer l's colour is
+ * c_l = scrub(lacc[l] / accumulator row 3) and goes through cl2_denoise's a-trous passes with its own sigma_color[l]; sigma_depth and
+ * sigma_albedo are shared.  Per pixel and layer these are cl2_denoise's float operations on the same operands in the same order:
+ * out_layers[l] holds the bytes cl2_denoise(iterations, sigma_color[l], ...) returns on a handle with the same features whose
+ * accumulator rows 0..2 are lacc[l].  The part of a tap weight that has no colour in it -- B3-spline, normal, depth, albedo -- is
+ * computed once per tap and pass and shared by the layers.  out_sum = F_0, then + F_l for l = 1 .. L-1: one float32 add per
+ * component, in layer order.  iterations = 0 returns the layer pictures themselves (Renderer.layer_radiance() on the device).
+ * Either output may be NULL, not both; n_layer_floats = n_layers*3*W*H ([L][H][W][3], b, g, r), n_sum_floats = 3*W*H.
+ * Checks: cl2_denoise's for every sigma_color[l] (iterations in 0..12, positive finite sigmas, the two underflow refusals);
+ * CL2_E_INVALID also for a NULL handle (nothing is dereferenced), a NULL sigma_color, both outputs NULL, a wrong size, and for
+ * cl2_keep_layer_picture a layer outside -1..L-1; CL2_E_STATE without a layer table, while lacc is invalid (cl2_read_layers_packed's
+ * condition and message) and without current features.
+ * cl2_keep_layer_picture: the same launches for one layer (only that layer is filtered) or, with layer = -1, for the sum; the result
+ * becomes the KEPT picture (kind 6 / 7) under cl2_keep_picture's rules: a snapshot, nothing is copied to the host, a refused call
+ * leaves the previous kept picture, a HIP failure part way through leaves kind 0.  cl2_read_picture, cl2_picture_log_sum and
+ * cl2_picture_tone_map serve kinds 6 and 7 like any other; cl2_keep_picture(0) drops them; cl2_keep_picture still takes 0..4 only.
+ * Memory: two working buffers of n_layers*W*H float4, 32 bytes per layer and pixel (1080p: 199 MB with 3 layers, 531 MB with 8),
+ * allocated by the first of these calls and released when the table changes, is switched off or the handle is destroyed.
+ * Both calls drain the handle's streams and write only these buffers and, for the second, the kept picture: accumulators, lacc,
+ * moments, buckets, seeds, features, counters and the buffers of cl2_denoise are read at most. */
+int cl2_denoise_layers(cl2_renderer* r, int iterations, const float* sigma_color /* [n_layers] */, float sigma_depth,
+                       float sigma_albedo, float* out_layers /* [L][H][W][3] b, g, r, or NULL */, size_t n_layer_floats,
+                       float* out_sum /* (H, W, 3), or NULL */, size_t n_sum_floats);
+int cl2_keep_layer_picture(cl2_renderer* r, int layer /* 0..L-1, or -1 = the sum */, int iterations,
+                           const float* sigma_color /* [n_layers] */, float sigma_depth, float sigma_albedo);
 
 #ifdef __cplusplus
 }
