@@ -771,7 +771,16 @@ int launch_resolve(cl2_renderer* r, hipStream_t st, const PathBufs* set, int cs,
                                            r->d_lay_agg, r->d_lay_light);
                 }, mats_lds, r->reproducible, map != nullptr, masked, layered);
             };
-            if (three_waves) launch(int_c<3>{}); else launch(int_c<2>{});
+            // The slim kernel (connect_resolve.hpp): three waves per SIMD, and room left on the SIMD and in LDS for a workgroup of
+            // the subpath stage, whose launches of later samples are pending on the other stream.  Its DET form fits three waves too.
+            if (resolve_runs_slim(r->bvh.n_tris, r->n_mats, map != nullptr, masked, layered, r->debug_flags)) {
+                with_flags([&](auto DET) {
+                    hipLaunchKernelGGL((k_connect_resolve_slim<DET.value>), dim3(grid_for(B)), dim3(BLOCK), 0, st, B, lp, cp, r->d_mats,
+                                       r->n_mats, r->d_tri_shade, r->cam_tris, r->cam, r->d_cmask[cs], r->d_chit[cs], r->d_agg,
+                                       r->d_light_image, r->d_uni, r->d_stats, r->debug_flags, r->d_det_keys, r->d_det_vals, map,
+                                       (unsigned long long)r->strategy_mask, r->lcodes, r->d_lay_agg, r->d_lay_light);
+                }, r->reproducible);
+            } else if (three_waves) launch(int_c<3>{}); else launch(int_c<2>{});
         }
     }
     HIP_TRY(r, hipGetLastError());

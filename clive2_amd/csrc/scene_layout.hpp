@@ -29,6 +29,21 @@ struct CameraRec {   // byte-identical to struct Camera, trace.metal:72-85
 
 struct MaterialDev { float4 color_type; float4 emission_alpha; float ior; float pad[3]; };  // 48 B
 
+// The slim resolve kernel (connect_resolve.hpp, k_connect_resolve_slim) keeps a light vertex's triangle and material byte in one
+// 32-bit word, {triangle << 8 | material}: a triangle index, or the -1 of "no triangle", must survive the shift as a signed value.
+constexpr int RESOLVE_SLIM_TRI_BITS = 23;
+constexpr int resolve_pack_tri(int tri, int meta) { return (int)(((unsigned)tri << 8) | ((unsigned)meta & 0xFFu)); }
+constexpr int resolve_packed_tri(int word) { return word >> 8; }
+constexpr int resolve_packed_mat(int word) { return word & 0xFF; }
+constexpr int RESOLVE_DEBUG_PARENT_BIT = 27;       // debug bit: launch k_connect_resolve where the slim kernel would run
+// Which resolve kernel a pass launches: the slim one for the combinations it is built for -- material table in LDS, no slot map,
+// no partial strategy mask, no layer table -- while every triangle index fits the packed word and the debug bit is clear.
+inline bool resolve_runs_slim(long long n_tris, int n_mats, bool mapped, bool masked, bool layered, int debug_flags) {
+    if (n_mats > LDS_MAT_CAP || mapped || masked || layered) return false;
+    if ((debug_flags >> RESOLVE_DEBUG_PARENT_BIT) & 1) return false;
+    return n_tris <= (1ll << RESOLVE_SLIM_TRI_BITS);
+}
+
 // The subpath kernel's static LDS: shading records and materials of small scenes (kernels.hpp, ShadeSrc).
 struct ShadeLds {
     float4 tri_shade[4 * SHADE_LDS_CAP];

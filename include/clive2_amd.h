@@ -305,11 +305,14 @@ int cl2_read_walk_tallies(cl2_renderer* r, cl2_walk_tallies* out);
  *   bit 26      flat pruned table of an LDS-resident tree (closest_hit_flat): the loop with the next-record index clamped on the
  *               scalar unit and the leaf record read in three steps (closest_hit_flat_clamped) instead of the one that keeps the
  *               record address in a vector register and fetches past the last triangle into pad records, for A/B runs and tests
+ *   bit 27      resolve stage: launch k_connect_resolve, the kernel that holds every register of its SIMDs, where the slim one
+ *               that leaves room for a wave of the subpath stage would run (csrc/connect_resolve.hpp: k_connect_resolve_slim),
+ *               for A/B runs and tests
  * Any other bit is refused (CL2_E_INVALID).  Bits 0-2 exist ONLY in the test variant of the library
  * (libclive2_amd_test.so, -DCL2_TEST_VARIANT), where they switch parts of the resolve stage off for timing
  * dissections -- bit 0 the t = 1 splat atomics, bit 1 / bit 2 the t >= 2 / t == 1 strategy pairs -- and make the
  * render INVALID; the shipped library refuses them. */
-#define CL2_DEBUG_KNOWN_BITS 0x06FF7FFF
+#define CL2_DEBUG_KNOWN_BITS 0x0EFF7FFF
 int cl2_set_debug_flags(cl2_renderer* r, int flags);
 /* Reproducible light image, off by default.  The reference's light-image chain (sort by target pixel, per-pixel gather:
  * src/renderer.py:97-111, :213-250, src/trace.metal:872-964) is deterministic; the float atomics that replace it add a pixel's
