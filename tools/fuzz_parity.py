@@ -1,6 +1,7 @@
 """Differential fuzzing: random scenes (camera pose, meshes, materials, frame size, launch organisation)
 rendered by the HIP path and by the oracle; subpaths, RNG state and filter aggregators must match bit for
-bit, the accumulated image to 5e-5.   python tools/fuzz_parity.py [n_scenes] [first_seed]"""
+bit, the accumulated image to 5e-5.   python tools/fuzz_parity.py [--masked] [n_scenes] [first_seed]
+--masked: strategy masks and layer tables against the masked oracle instead (masked_main)."""
 import os
 import sys
 import time
@@ -64,9 +65,39 @@ def random_scene(rng, max_members=None):
             (w, h, len(specs), str(builder), 'open' if room is not None else 'closed') + ((f"mm{max_members}",) if max_members else ()))
 
 
+def masked_main(n, first):
+    """--masked: per scene a drawn strategy mask, layer table, stream count (1 or 2), traversal mode (0..2) and reproducible
+    switch; the masked render and the layered render of two passes against the masked oracle (tests/masked_oracle.py: device_check,
+    the check of tests/test_gpu_masked_oracle.py::test_random_scene_masked_and_layered) -- bytes under the switch, else at the
+    light image's tolerance."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import masked_oracle as mo
+    from clive2_amd.renderer import stream_seeds
+    orc.build()
+    bad = 0
+    for k in range(first, first + n):
+        rng = np.random.RandomState(1000 + k)
+        scene, desc = random_scene(rng)
+        case = mo.draw_case(rng)
+        B = scene.pixel_width * scene.pixel_height
+        t0 = time.time()
+        problems, left_out = mo.device_check(scene, stream_seeds(B, case["K"], seed=k), case, passes=2)
+        print(f"scene {k}: {desc} tris={len(scene.triangles)} mask={case['mask']:#x} table={[hex(m) for m in case['table'].values()]} "
+              f"K={case['K']} mode={case['mode']} repro={int(case['reproducible'])} left_out={left_out} "
+              f"{'OK' if not problems else 'MISMATCH: ' + '; '.join(problems)} ({time.time() - t0:.1f}s)", flush=True)
+        bad += bool(problems)
+    print(f"RESULT: {n - bad}/{n} scenes match the masked oracle")
+    return 1 if bad else 0
+
+
 def main():
+    masked = "--masked" in sys.argv
+    if masked:
+        sys.argv.remove("--masked")
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    if masked:
+        return masked_main(n, first)
     orc.build()
     bad = 0
     for k in range(first, first + n):
