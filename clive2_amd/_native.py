@@ -100,6 +100,7 @@ EXPORTS = [
     "cl2_set_strategy_mask", "cl2_get_strategy_mask",
     "cl2_set_layers", "cl2_get_layers", "cl2_read_layers_packed", "cl2_write_layers_packed",
     "cl2_denoise_layers", "cl2_keep_layer_picture",
+    "cl2_wide_stack_capacity",
 ]
 
 
@@ -160,6 +161,7 @@ def lib(variant=None):
         L.cl2_get_sample_streams.argtypes = [C.c_void_p]
         L.cl2_set_traversal_order.argtypes = [C.c_void_p, C.c_int]
         L.cl2_get_traversal_order.argtypes = [C.c_void_p]
+        L.cl2_wide_stack_capacity.argtypes = [C.c_void_p]
         L.cl2_set_connection_query.argtypes = [C.c_void_p, C.c_int]
         L.cl2_get_connection_query.argtypes = [C.c_void_p]
         L.cl2_connection_query_active.argtypes = [C.c_void_p]

@@ -29,10 +29,7 @@
 
 namespace cl2 {
 
-#ifndef CL2_WIDE_STACK_LDS
-#define CL2_WIDE_STACK_LDS 8
-#endif
-constexpr int WIDE_STACK_LDS = CL2_WIDE_STACK_LDS;
+// (WIDE_STACK_LDS and WIDE_STACK_OVERFLOW: scene_layout.hpp, shared with the host-side sizing of the overflow array.)
 // Triangle pairs a lane in a leaf tests per pass.  The pass -- its refill check, its node block for the other lanes, its
 // bookkeeping, its dependent fetch -- is the unit of cost of the persistent walks, so a leaf of three or four
 // triangles should not take two of them: a second pair in the same pass (fetched after the first is tested) took the
@@ -44,10 +41,15 @@ constexpr int WIDE_STACK_LDS = CL2_WIDE_STACK_LDS;
 // (Two node visits per pass, by the same reasoning, do NOT pay: 3.80 -> 4.12 ms; nor does a second triangle round in the
 // binary walks, whose pass already tests the first triangles of a leaf together with the node visit that enters it:
 // whole-subpath launch 5.87 -> 6.30 ms on the glass scene, connection launch of the 1M-triangle scene 15.8 -> 16.3 ms.)
-// 2 x the reference's 64-entry stack bound + slack: the walk in the reference's child order cannot exceed it (Q18 check at upload).
-// The nearest-first walk (ORDER) pushes siblings in another order, and its depth is not bounded by the pending depth the
-// overflow sizing rests on.
-constexpr int WIDE_STACK_OVERFLOW = 136;
+// The pushes below are not clamped: the host sizes the per-lane overflow array so that no walk can leave it (scene_prep.hpp,
+// wide_overflow_entries), from two static bounds of the uploaded tree.
+//   * Reference child order: every entry pending on the reference's stack stands for at most two entries here, plus what a visit
+//     pushes -- 2 x max_pending + 4 <= WIDE_STACK_OVERFLOW = 2 x the reference's 64-entry bound + slack (Q18 check at upload).
+//   * Nearest first (ORDER): any slot of a node may be taken first and up to three siblings wait, so the depth is bounded by
+//     order_depth = the largest sum of (slots - 1) along a root-to-leaf path of the collapse, whatever passes; a tree whose
+//     order_depth exceeds WIDE_STACK_LDS + WIDE_STACK_OVERFLOW is refused for that order (cl2_set_traversal_order, cl2_upload_scene).
+// Both are tested against a restatement of this walk's push and pop rules (tests/wide_walk_reference.py) on balanced, chain-shaped,
+// random and GPU-built trees: tests/test_wide_stack_cpu.py; on the device: tests/test_gpu_wide_stack.py.
 
 #ifdef CL2_WALK_HISTO
 // instrumentation build only (tools/exp_walk_histo.py): per pass of the wide walk, how many lanes visit a node / test triangles

@@ -95,7 +95,8 @@ struct cl2_renderer {
     float4* d_fast = nullptr;            // pruned record table of an LDS-resident tree (scene_prep.hpp); bvh.n_fast_nodes == 0: none
     WideView wide{};
     int2* d_wide_ovf = nullptr;          // per-lane stack overflow of the wide launches (one region per stage: [2]); allocated by the first wide launch
-    int wide_ovf_entries = 0;            // entries per lane: the deepest stack this tree can produce (cl2_upload_scene)
+    int wide_ovf_entries = 0;            // entries per lane: wide_overflow_entries of this tree in the CURRENT child order (cl2_upload_scene, cl2_set_traversal_order)
+    int max_pending = 0, order_depth = 0; // the uploaded tree's two stack depths (scene_prep.hpp): what that size is computed from
     CameraRec cam{};
 
     // state
@@ -439,10 +440,15 @@ inline int persistent_grid_conn(const cl2_renderer* r) {
 // One persistent launch of the exact 4-wide walk.  `stage` 0 = subpath stage, 1 = connection stage: each has its own
 // stack-overflow region, since the two run side by side in the sample pipeline.
 // The per-lane stack of a wide walk keeps its first entries in LDS and the rest in a global array.  How deep it can get
-// is a static property of the tree: every entry pending on the reference's stack (at most `pending` of them, counted at
-// upload) stands for at most two wide-stack entries, plus the four a visit pushes.  The array is sized for that bound
-// (not for the 2 x 64 + 8 any admissible tree could reach) and exists only once a wide launch has been asked for:
-// an LDS-resident scene never takes the wide walk on its own, and a turntable builds one renderer per frame.
+// is a static property of the tree and of the child order.  In the reference's order every entry pending on the reference's
+// stack (at most `max_pending` of them, counted at upload) stands for at most two wide-stack entries, plus the four a visit
+// pushes; nearest first, the bound is the tree's order_depth instead (scene_prep.hpp: build_wide, wide_overflow_entries; both
+// bounds are tested against the walk's push rule in tests/test_wide_stack_cpu.py and on the device in
+// tests/test_gpu_wide_stack.py).  The kernel does not clamp its pushes: wide_ovf_entries is recomputed whenever the scene or
+// the order changes, and a tree that the cap cannot serve nearest first is refused there, so no launch sees a stack deeper
+// than its array.  The array is sized for that bound (not for the 2 x 64 + 8 any admissible tree could reach) and exists only
+// once a wide launch has been asked for: an LDS-resident scene never takes the wide walk on its own, and a turntable builds
+// one renderer per frame.
 int ensure_wide_overflow(cl2_renderer* r) {
     if (r->d_wide_ovf) return CL2_OK;
     const size_t lanes = (size_t)persistent_grid() * BLOCK;
@@ -1069,6 +1075,13 @@ int cl2_upload_scene(cl2_renderer* r, const void* boxes_v, int n_boxes, const vo
     const std::string msg = prepare_scene(boxes_v, n_boxes, tris_v, n_tris, mats_v, n_mats, camera_v, light_tris_v, light_areas,
                                           light_tri_index, light_count, r->W, r->H, p);
     if (!msg.empty()) return fail(r, CL2_E_INVALID, msg);
+    // the wide walk's stack in the current child order (see ensure_wide_overflow): a tree too deep for it is not uploaded
+    const int ovf_entries = p.n_wide > 0 ? wide_overflow_entries(p.max_pending, p.order_depth, r->traversal_order) : 0;
+    if (ovf_entries < 0) {
+        r->scene_ok = false;
+        return fail(r, CL2_E_INVALID, "tree too deep for the nearest-first child order: its 4-wide stack can reach " + std::to_string(p.order_depth) +
+                                      " entries, the limit is " + std::to_string(WIDE_STACK_LDS + WIDE_STACK_OVERFLOW) + " (cl2_set_traversal_order(0) first)");
+    }
 
     HIP_TRY(r, hipSetDevice(r->device));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
@@ -1091,8 +1104,8 @@ int cl2_upload_scene(cl2_renderer* r, const void* boxes_v, int n_boxes, const vo
         TRY(upload(r, &r->d_wide, p.wide.data(), p.wide.size()));
         TRY(upload(r, &r->d_tri_rank, p.tri_rank.data(), p.tri_rank.size()));
         // deepest wide stack of THIS tree (see ensure_wide_overflow); a new scene may need a different size
-        const int entries = std::min((int)WIDE_STACK_OVERFLOW, 2 * p.max_pending + 4);
-        if (entries != r->wide_ovf_entries) { dev_free(r, r->d_wide_ovf); r->wide_ovf_entries = entries; }
+        if (ovf_entries != r->wide_ovf_entries) { dev_free(r, r->d_wide_ovf); r->wide_ovf_entries = ovf_entries; }
+        r->max_pending = p.max_pending; r->order_depth = p.order_depth;
         const BoxRec& root = static_cast<const BoxRec*>(boxes_v)[0];
         r->wide.nodes = r->d_wide; r->wide.tris = r->d_tris; r->wide.tris36 = r->d_tris36;
         r->wide.tri_rank = r->d_tri_rank + 1;   // read on exact-t ties only (ORDER); [-1] ranks "nothing held"
@@ -1853,10 +1866,24 @@ int cl2_set_traversal_order(cl2_renderer* r, int order) {
     if (order == 1 && r->connection_query == 1) return fail(r, CL2_E_INVALID, "the seeded connection query keeps the reference's child order: cl2_set_connection_query(0) first");
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));
+    if (r->n_wide > 0) {
+        // the overflow array of the wide walk's stack is sized for the order (ensure_wide_overflow reallocates at the next launch)
+        const int entries = wide_overflow_entries(r->max_pending, r->order_depth, order);
+        if (entries < 0)
+            return fail(r, CL2_E_INVALID, "tree too deep for the nearest-first child order: its 4-wide stack can reach " + std::to_string(r->order_depth) +
+                                          " entries, the limit is " + std::to_string(WIDE_STACK_LDS + WIDE_STACK_OVERFLOW));
+        if (entries != r->wide_ovf_entries) { dev_free(r, r->d_wide_ovf); r->wide_ovf_entries = entries; }
+    }
     r->traversal_order = order;
     return CL2_OK;
 }
 int cl2_get_traversal_order(const cl2_renderer* r) { return r ? r->traversal_order : CL2_E_INVALID; }
+/* Stack entries a lane of the 4-wide walk has for the uploaded scene in the current child order: those in LDS plus those of the
+ * global overflow array.  0: no scene, or a scene without a 4-wide collapse. */
+int cl2_wide_stack_capacity(const cl2_renderer* r) {
+    if (!r) return CL2_E_INVALID;
+    return (r->scene_ok && r->n_wide > 0) ? WIDE_STACK_LDS + std::max(r->wide_ovf_entries, 1) : 0;
+}
 /* What a connection ray asks of the tree.  0 (default) = its closest hit, as the reference.  1 = for a t >= 2 pair, whether the camera
  * vertex's triangle is what the ray sees: the walk starts from the target's distance and stops at the first blocker (csrc/bvh_wide.hpp
  * VIS).  Opt-in and NOT the parity path: the verdict is the reference's except where a hit lies in front of its own leaf box.  Applies

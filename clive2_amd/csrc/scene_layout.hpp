@@ -10,7 +10,14 @@ constexpr int LDS_TRI_CAP = 512;    // triangles staged in LDS when the whole sc
 constexpr int LDS_TRI_PADS = 2;     // pad records behind the staged triangles: fetched by the flat walk, never tested (bvh_traverse.hpp)
 constexpr int LEAF_PACK_MAX = 16;   // triangles per leaf record
 constexpr int WIDE_EMPTY = (int)0x80000000;   // ref of an empty slot of a wide node (bvh_wide.hpp)
-constexpr int SHADE_LDS_CAP = 128;  // shading triangles staged in LDS by the subpath kernel (64 B each)
+// Per-lane stack of the 4-wide walk (bvh_wide.hpp): the first WIDE_STACK_LDS entries in LDS, at most WIDE_STACK_OVERFLOW more in a
+// per-lane global array that scene_prep.hpp's wide_overflow_entries sizes from the tree.
+#ifndef CL2_WIDE_STACK_LDS
+#define CL2_WIDE_STACK_LDS 8
+#endif
+constexpr int WIDE_STACK_LDS = CL2_WIDE_STACK_LDS;
+constexpr int WIDE_STACK_OVERFLOW = 136;
+constexpr int SHADE_LDS_CAP = 128; // shading triangles staged in LDS by the subpath kernel (64 B each)
 constexpr int LDS_MAT_CAP = 32;     // materials staged in LDS by the subpath kernel
 
 // The triangles of the camera quad (is_camera, scene.py): the t = 1 pairs ask whether the triangle their ray hit is one of

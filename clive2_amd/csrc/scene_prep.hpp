@@ -27,6 +27,7 @@ struct PreparedScene {
     std::vector<MaterialDev> mats;
     std::vector<int> tri_rank;
     int n_records = 0, n_top = 0, n_fast = 0, fast_flat = 0, n_wide = 0, max_pending = 0;
+    int order_depth = 0;                 // deepest stack of the 4-wide walk in ANY child order (build_wide); 0 without a collapse
     CamTris cam_tris{0, {0, 0, 0, 0}};
     CameraRec cam{};
 };
@@ -144,6 +145,9 @@ inline std::string check_indices(const Scene& s) {
 // 6. 4-wide collapse for the exact wide walk (bvh_wide.hpp).  Conditions: the root is an inner box, every box nests its children
 // exactly (what the exactness argument rests on; true for trees that np_flatten_bvh or either native builder made, not guaranteed
 // for hand-made Box[] arrays) and no leaf exceeds one record.  Returns whether the boxes nest that way.
+// order_depth: a walk that stands at a wide node has left at most (slots - 1) of each node on its path on the stack, whichever slot
+// it took first and whichever boxes passed, so D(node) = (slots - 1) + max over the node's inner slots of D(slot), D(leaf) = 0, bounds
+// the stack of the walk in any child order (the nearest-first walk's bound: wide_overflow_entries).
 inline bool build_wide(const Scene& s, PreparedScene& out) {
     const BoxRec* boxes = s.boxes;
     bool ok = s.n_boxes >= 3 && boxes[0].right == 0;
@@ -194,6 +198,15 @@ inline bool build_wide(const Scene& s, PreparedScene& out) {
         for (int c = 0; c < 6; c++) out.wide[(size_t)8 * wn + c] = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
         out.wide[(size_t)8 * wn + 6] = make_float4(as_f(ref[0]), as_f(ref[1]), as_f(ref[2]), as_f(ref[3]));
     }
+    std::vector<int> depth((size_t)out.n_wide, 0);
+    for (int wn = out.n_wide - 1; wn >= 0; wn--) {                  // breadth-first numbering: a node's inner slots come after it
+        int sl[4];
+        const int n = slots_of(order[wn], sl);
+        int below = 0;
+        for (int k = 0; k < n; k++) if (boxes[sl[k]].right == 0) below = std::max(below, depth[wide_of[sl[k]]]);
+        depth[wn] = n - 1 + below;
+    }
+    out.order_depth = depth[0];
     return true;
 }
 
@@ -340,6 +353,18 @@ inline void pack_wide_extras(const Scene& s, const Order& o, PreparedScene& out)
 }
 
 }  // namespace prep
+
+// Entries per lane of the wide walk's global overflow array (bvh_wide.hpp) for a tree with these two depths and this child order
+// (cl2_set_traversal_order), or -1: the tree cannot be served in that order.  Order 0, the reference's: twice the reference's
+// pending depth plus the four a visit pushes.  Order 1, nearest first: the pending depth says nothing about it; what bounds it is
+// order_depth (build_wide), of which WIDE_STACK_LDS entries live in LDS -- never less than order 0's size, with the same slack, and
+// never beyond what order_depth itself needs at the cap.  tests/test_wide_stack_cpu.py holds both against the walk's push rule.
+inline int wide_overflow_entries(int max_pending, int order_depth, int order) {
+    const int reference = std::min(WIDE_STACK_OVERFLOW, 2 * max_pending + 4);
+    if (order == 0) return reference;
+    if (order_depth > WIDE_STACK_LDS + WIDE_STACK_OVERFLOW) return -1;
+    return std::max(reference, std::min(WIDE_STACK_OVERFLOW, order_depth - WIDE_STACK_LDS + 4));
+}
 
 // Validates cl2_upload_scene's arguments against a W x H renderer and builds the device records into `out`: "" on success,
 // else the refusal (the checks run in a fixed order, and the first that fails is reported).

@@ -468,6 +468,11 @@ class Renderer:
     def traversal_order(self):
         return int(self._L.cl2_get_traversal_order(self._h))
 
+    def wide_stack_capacity(self):
+        """Stack entries a lane of the 4-wide walk has for the uploaded scene in the current child order (LDS entries plus the
+        per-lane overflow array, sized from the tree: cl2_wide_stack_capacity); 0 when the scene has no 4-wide collapse."""
+        return int(self._L.cl2_wide_stack_capacity(self._h))
+
     def set_connection_query(self, mode=1):
         """What a connection ray asks of the tree (cl2_set_connection_query): 0 = its closest hit (the default, as the reference),
         1 = for a t >= 2 pair, whether the camera vertex's triangle is what the ray sees -- a walk seeded with that triangle, which

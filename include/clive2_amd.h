@@ -337,6 +337,13 @@ int cl2_get_reproducible(const cl2_renderer* r);
  * either way).  No reference counterpart (src/trace.metal:144-176 has one order). */
 int cl2_set_traversal_order(cl2_renderer* r, int order);
 int cl2_get_traversal_order(const cl2_renderer* r);
+/* The 4-wide walk keeps a per-lane stack whose pushes are not clamped: the library sizes it from the uploaded tree and the child
+ * order -- order 0 from the depth of the reference's stack, order 1 from the tree's deepest sum of (slots - 1) over a path of its
+ * 4-wide collapse, which no walk in any order exceeds.  A tree whose bound for order 1 is beyond the stack's cap is refused
+ * (CL2_E_INVALID) by cl2_set_traversal_order(1), and by cl2_upload_scene while order 1 is set; order 0 takes every tree
+ * cl2_upload_scene accepts.  cl2_wide_stack_capacity: the entries a lane has for the current scene and order (0: no scene, or
+ * no 4-wide collapse). */
+int cl2_wide_stack_capacity(const cl2_renderer* r);
 /* What a connection ray asks of the tree (additions to ABI 6).  mode = 0 (default): its closest hit, as the reference
  * (src/trace.metal:144-176).  mode = 1: for a pair with t >= 2 the resolve stage reads one bit of that result -- whether the hit
  * triangle is the camera vertex's triangle T -- so the ray becomes a VISIBILITY query seeded with T: T is tested first, the walk

@@ -47,8 +47,14 @@ int sp_scalar(void* h, const char* name) {
     if (!std::strcmp(name, "fast_flat")) return s.fast_flat;
     if (!std::strcmp(name, "n_wide")) return s.n_wide;
     if (!std::strcmp(name, "max_pending")) return s.max_pending;
+    if (!std::strcmp(name, "order_depth")) return s.order_depth;
     return -1;
 }
+
+// cl2::wide_overflow_entries and the two capacities it works with
+int sp_wide_overflow_entries(int max_pending, int order_depth, int order) { return cl2::wide_overflow_entries(max_pending, order_depth, order); }
+int sp_wide_stack_lds() { return cl2::WIDE_STACK_LDS; }
+int sp_wide_stack_overflow() { return cl2::WIDE_STACK_OVERFLOW; }
 
 void sp_free(void* h) { delete static_cast<PreparedScene*>(h); }
 

@@ -18,7 +18,7 @@ from tree_reference import pending_depths
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARRAYS = ("nodes", "fast", "wide", "tris", "tris36", "shade", "ltris", "mats", "tri_rank", "cam_tris")
-SCALARS = ("n_records", "n_top", "n_fast", "fast_flat", "n_wide", "max_pending")
+SCALARS = ("n_records", "n_top", "n_fast", "fast_flat", "n_wide", "max_pending", "order_depth")
 
 
 @pytest.fixture(scope="module")
@@ -136,22 +136,22 @@ def digest(out):
 PINS = {
     "cornell": {"nodes": "8038b7e1dc5a948a", "fast": "49a4cd6313e82a3e", "wide": "6124676fe21c674f", "tris": "b7f6e586fcb38296", "tris36": "e3b19db4e2683619",
         "shade": "3aff54db0c24b2ea", "ltris": "296bcada34d57497", "mats": "d2dbb3e27daba0c3", "tri_rank": "af53d6eaacd050da", "cam_tris": "bfce42ee6f1de630",
-        "n_records": 5, "n_top": 0, "n_fast": 3, "fast_flat": 1, "n_wide": 1, "max_pending": 1},
+        "n_records": 5, "n_top": 0, "n_fast": 3, "fast_flat": 1, "n_wide": 1, "max_pending": 1, "order_depth": 2},
     "glass": {"nodes": "0aefc6b8adbbf810", "fast": "1c40ea03b23c8c1e", "wide": "eaab2425f6bd3b3a", "tris": "a59a769290f0ff25", "tris36": "4c781396304f2bb2",
         "shade": "e4aa70c826a02875", "ltris": "f273723a1f0621a5", "mats": "0c17a38b488ba004", "tri_rank": "83573ba26302b4a3", "cam_tris": "c7bd5e674ae7b286",
-        "n_records": 121, "n_top": 0, "n_fast": 119, "fast_flat": 0, "n_wide": 34, "max_pending": 6},
+        "n_records": 121, "n_top": 0, "n_fast": 119, "fast_flat": 0, "n_wide": 34, "max_pending": 6, "order_depth": 13},
     "mesh": {"nodes": "75c8df3c6a76d303", "fast": "e3b0c44298fc1c14", "wide": "7a53536648ba86fd", "tris": "1f38df8d2b8c4c8e", "tris36": "63835a46c37f22e0",
         "shade": "4761c8910a96a8d6", "ltris": "f273723a1f0621a5", "mats": "d2dbb3e27daba0c3", "tri_rank": "ced3509026d1fe54", "cam_tris": "c7bd5e674ae7b286",
-        "n_records": 839, "n_top": 512, "n_fast": 0, "fast_flat": 0, "n_wide": 207, "max_pending": 9},
+        "n_records": 839, "n_top": 512, "n_fast": 0, "fast_flat": 0, "n_wide": 207, "max_pending": 9, "order_depth": 18},
     "big_leaf": {"nodes": "4019f54a80f2c8ac", "fast": "e3b0c44298fc1c14", "wide": "e3b0c44298fc1c14", "tris": "a59a769290f0ff25", "tris36": "e3b0c44298fc1c14",
         "shade": "e4aa70c826a02875", "ltris": "f273723a1f0621a5", "mats": "0c17a38b488ba004", "tri_rank": "e3b0c44298fc1c14", "cam_tris": "c7bd5e674ae7b286",
-        "n_records": 23, "n_top": 0, "n_fast": 0, "fast_flat": 0, "n_wide": 0, "max_pending": 1},
+        "n_records": 23, "n_top": 0, "n_fast": 0, "fast_flat": 0, "n_wide": 0, "max_pending": 1, "order_depth": 0},
     "not_nested": {"nodes": "5fc508789124f88b", "fast": "e3b0c44298fc1c14", "wide": "e3b0c44298fc1c14", "tris": "b7f6e586fcb38296", "tris36": "e3b0c44298fc1c14",
         "shade": "3aff54db0c24b2ea", "ltris": "296bcada34d57497", "mats": "d2dbb3e27daba0c3", "tri_rank": "e3b0c44298fc1c14", "cam_tris": "bfce42ee6f1de630",
-        "n_records": 5, "n_top": 0, "n_fast": 0, "fast_flat": 0, "n_wide": 0, "max_pending": 1},
+        "n_records": 5, "n_top": 0, "n_fast": 0, "fast_flat": 0, "n_wide": 0, "max_pending": 1, "order_depth": 0},
     "chain": {"nodes": "7ebce829155c58c1", "fast": "c02f39eb7478d9e3", "wide": "df8e9b6f9b304e96", "tris": "a59a769290f0ff25", "tris36": "4c781396304f2bb2",
         "shade": "e4aa70c826a02875", "ltris": "f273723a1f0621a5", "mats": "0c17a38b488ba004", "tri_rank": "ea3548ec5a662bbd", "cam_tris": "c7bd5e674ae7b286",
-        "n_records": 49, "n_top": 0, "n_fast": 30, "fast_flat": 0, "n_wide": 12, "max_pending": 24},
+        "n_records": 49, "n_top": 0, "n_fast": 30, "fast_flat": 0, "n_wide": 12, "max_pending": 24, "order_depth": 24},
 }
 
 
