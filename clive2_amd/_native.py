@@ -101,6 +101,7 @@ EXPORTS = [
     "cl2_set_layers", "cl2_get_layers", "cl2_read_layers_packed", "cl2_write_layers_packed",
     "cl2_denoise_layers", "cl2_keep_layer_picture",
     "cl2_wide_stack_capacity",
+    "cl2_denoise_error",
 ]
 
 
@@ -186,6 +187,8 @@ def lib(variant=None):
         L.cl2_denoise.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t]
         L.cl2_denoise_guided.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_size_t]
+        L.cl2_denoise_error.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
+                                        C.c_uint32, C.c_double, C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         L.cl2_set_error_tracking.argtypes = [C.c_void_p, C.c_int]
         L.cl2_get_error_tracking.argtypes = [C.c_void_p]
         L.cl2_read_moments_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]

@@ -23,6 +23,7 @@
 #include "../../include/clive2_amd.h"
 #include "kernels.hpp"
 #include "denoise.hpp"
+#include "denoise_error.hpp"
 #include "denoise_guided.hpp"
 #include "denoise_layers.hpp"
 #include "denoise_robust.hpp"
@@ -164,6 +165,11 @@ struct cl2_renderer {
     float4* d_dn[2] = {nullptr, nullptr};   // ping-pong colour of the filter passes
     float* d_dn_out = nullptr;           // (H, W, 3) result of the last pass
     float* d_dn_var = nullptr;           // (H, W) guide variance after the last pass of cl2_denoise_guided (denoise_guided.hpp)
+    // the error estimate of the filtered picture (cl2_denoise_error, denoise_error.hpp), allocated by its first call
+    float4 *d_de_y = nullptr, *d_de_a = nullptr, *d_de_yp = nullptr;   // y, A = (a, code), y' of the current probe
+    float* d_de_fy = nullptr;            // (H, W, 3) F(y); F(y') is the filters' d_dn_out
+    float* d_de_map = nullptr;           // (H, W) the per-pixel estimate
+    double* d_de_sum = nullptr;          // [W*H] sum over the probes of u g, then [DE_SUMS][ERR_BLOCKS] partials + [8] result
 
     // error tracking (cl2_set_error_tracking, error_estimate.hpp): second moments of the addends, [8][W*H], while tracking is on
     float* d_mom = nullptr;
@@ -2371,7 +2377,8 @@ int need_filter_buffers(cl2_renderer* r) {
 namespace {
 // cl2_denoise after its output checks, shared with cl2_keep_picture: the remaining checks and every launch; the last launch
 // writes the (H, W, 3) picture to `dst` (device memory; nullptr: d_dn_out)
-int run_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* dst) {
+// the argument and feature checks of cl2_denoise (also cl2_denoise_error's for kind 0)
+int denoise_checks(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo) {
     if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
     auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
     if (bad(sigma_color) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
@@ -2380,19 +2387,20 @@ int run_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
     if (iterations >= 1 && std::ldexp(sigma_color * sigma_color, -2 * (iterations - 1)) < FLT_MIN)
         return fail(r, CL2_E_INVALID, "sigma_color^2 * 4^-(iterations-1) underflows float32");
     if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
-    const size_t FB = (size_t)r->FB;
-    TRY(need_filter_buffers(r));
-    if (!dst) dst = r->d_dn_out;
+    return CL2_OK;
+}
+
+// cl2_denoise's passes from a prepared input `src` (pass 0 reads it; the later ones ping-pong d_dn[1], d_dn[0]); the last launch
+// writes the (H, W, 3) picture to `dst`.  With iterations = 0 nothing is launched: whoever made `src` wrote `dst` too.
+int denoise_passes(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, const float4* src,
+                   float* dst) {
     hipStream_t st = r->stream;
-    hipLaunchKernelGGL(k_denoise_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc, r->d_dn[0],
-                       iterations == 0 ? dst : (float*)nullptr);
-    HIP_TRY(r, hipGetLastError());
     const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
     const float den_a = sigma_albedo * sigma_albedo;
     for (int i = 0; i < iterations; i++) {
         const int step = 1 << i;
         const float den_c = std::ldexp(sigma_color * sigma_color, -2 * i);      // sigma_color^2 * 4^-i, exact scaling
-        const float4* cin = r->d_dn[i & 1];
+        const float4* cin = i == 0 ? src : r->d_dn[i & 1];
         float4* cout = r->d_dn[(i + 1) & 1];
         float* out3 = i == iterations - 1 ? dst : nullptr;
         auto pass = [&](auto LDS_STEP) {
@@ -2401,6 +2409,18 @@ int run_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_
         if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
         HIP_TRY(r, hipGetLastError());
     }
+    return CL2_OK;
+}
+
+int run_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* dst) {
+    TRY(denoise_checks(r, iterations, sigma_color, sigma_depth, sigma_albedo));
+    const size_t FB = (size_t)r->FB;
+    TRY(need_filter_buffers(r));
+    if (!dst) dst = r->d_dn_out;
+    hipLaunchKernelGGL(k_denoise_input, dim3(grid_for(FB)), dim3(BLOCK), 0, r->stream, r->FB, (const float*)r->d_acc, r->d_dn[0],
+                       iterations == 0 ? dst : (float*)nullptr);
+    HIP_TRY(r, hipGetLastError());
+    TRY(denoise_passes(r, iterations, sigma_color, sigma_depth, sigma_albedo, r->d_dn[0], dst));
     return drain(r);
 }
 }  // namespace
@@ -2654,13 +2674,39 @@ namespace {
 // cl2_denoise_guided / cl2_denoise_robust after their output checks, shared with cl2_keep_picture: the remaining checks and every
 // launch.  `robust`: the input pass reads the buckets (cl2_denoise_robust) instead of accumulators and moments.  `want_var`: the
 // guide variance is carried into d_dn_var.  The last launch writes the (H, W, 3) picture to `dst` (device memory; nullptr: d_dn_out).
-int run_guided(cl2_renderer* r, bool robust, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, bool want_var,
-               float* dst) {
+// the argument and feature checks of cl2_denoise_guided / cl2_denoise_robust (also cl2_denoise_error's for kind 1)
+int guided_checks(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo) {
     if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
     auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
     if (bad(sigma_luma) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
     if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
     if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
+    return CL2_OK;
+}
+
+// the guided passes from a prepared input `src`, as denoise_passes; `dvar`: where the last pass leaves its guide variance, or NULL
+int guided_passes(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, const float4* src,
+                  float* dst, float* dvar) {
+    hipStream_t st = r->stream;
+    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
+    const float den_a = sigma_albedo * sigma_albedo;
+    for (int i = 0; i < iterations; i++) {
+        const int step = 1 << i;
+        const float4* cin = i == 0 ? src : r->d_dn[i & 1];
+        float4* cout = r->d_dn[(i + 1) & 1];
+        float* out3 = i == iterations - 1 ? dst : nullptr;
+        auto pass = [&](auto LDS_STEP) {
+            hipLaunchKernelGGL(k_denoise_guided_pass<LDS_STEP.value>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
+        };
+        if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
+        HIP_TRY(r, hipGetLastError());
+    }
+    return CL2_OK;
+}
+
+int run_guided(cl2_renderer* r, bool robust, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, bool want_var,
+               float* dst) {
+    TRY(guided_checks(r, iterations, sigma_luma, sigma_depth, sigma_albedo));
     if (robust)
         TRY(robust_ready(r));
     else
@@ -2678,19 +2724,7 @@ int run_guided(cl2_renderer* r, bool robust, int iterations, float sigma_luma, f
         hipLaunchKernelGGL(k_denoise_guided_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc,
                            (const float*)r->d_mom, r->d_dn[0], iterations == 0 ? dst : (float*)nullptr, dvar);
     HIP_TRY(r, hipGetLastError());
-    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
-    const float den_a = sigma_albedo * sigma_albedo;
-    for (int i = 0; i < iterations; i++) {
-        const int step = 1 << i;
-        const float4* cin = r->d_dn[i & 1];
-        float4* cout = r->d_dn[(i + 1) & 1];
-        float* out3 = i == iterations - 1 ? dst : nullptr;
-        auto pass = [&](auto LDS_STEP) {
-            hipLaunchKernelGGL(k_denoise_guided_pass<LDS_STEP.value>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
-        };
-        if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
-        HIP_TRY(r, hipGetLastError());
-    }
+    TRY(guided_passes(r, iterations, sigma_luma, sigma_depth, sigma_albedo, r->d_dn[0], dst, dvar));
     return drain(r);
 }
 
@@ -2719,6 +2753,96 @@ int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float 
 int cl2_denoise_robust(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, float* out_bgr,
                        size_t n_floats, float* out_var, size_t n_var) {
     return guided_call(r, true, iterations, sigma_luma, sigma_depth, sigma_albedo, out_bgr, n_floats, out_var, n_var);
+}
+
+// The error estimate of the filtered picture (denoise_error.hpp): Monte-Carlo SURE over the passes of cl2_denoise
+// (kind 0) or cl2_denoise_guided (kind 1).  Reads accumulators, moments and features; writes its own buffers and the filters'
+// working buffers (d_dn[], d_dn_out); d_dn_var, a kept picture, seeds and counters are not touched.
+int cl2_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, float sigma_depth, float sigma_albedo, int probes,
+                      float epsilon, int correlated, uint32_t seed, double floor, double* out, float* out_map, size_t n_map,
+                      float* out_probe, size_t n_probe) {
+    STAGE_PROLOGUE(r);
+    if (!out) return fail(r, CL2_E_INVALID, "NULL output");
+    if (kind < 0 || kind > 1) return fail(r, CL2_E_INVALID, "denoise error: kind 0 (cl2_denoise) or 1 (cl2_denoise_guided)");
+    if (probes < 1 || probes > 16) return fail(r, CL2_E_INVALID, "probes must be in 1..16");
+    if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return fail(r, CL2_E_INVALID, "epsilon must be positive and finite");
+    if (correlated < 0 || correlated > 1) return fail(r, CL2_E_INVALID, "correlated must be 0 or 1");
+    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
+    const size_t FB = (size_t)r->FB;
+    if (out_map ? n_map != FB : n_map != 0) return fail(r, CL2_E_INVALID, "the error map must hold W*H floats (or be NULL with n_map 0)");
+    if (out_probe ? n_probe != 9 * FB : n_probe != 0)
+        return fail(r, CL2_E_INVALID, "the probe pictures must hold 3*(3*W*H) floats (or be NULL with n_probe 0)");
+    if (kind == 0) TRY(denoise_checks(r, iterations, sigma, sigma_depth, sigma_albedo));
+    else TRY(guided_checks(r, iterations, sigma, sigma_depth, sigma_albedo));
+    TRY(need_moments(r));
+    // the mean reconstruction weights of a camera sample, in float64 with erf (denoise_error.hpp)
+    DeKernel K;
+    {
+        const float ppw = r->cam.phys_width / r->cam.pixel_width, pph = r->cam.phys_height / r->cam.pixel_height;
+        const double s2 = (double)ppw * ppw + (double)pph * pph;
+        const double c[2] = {s2 / (2.0 * ppw * ppw), s2 / (2.0 * pph * pph)};
+        for (int a = 0; a < 2; a++)
+            for (int i = -1; i <= 1; i++) {
+                const double q = std::sqrt(c[a]);
+                const double k = 0.5 * std::sqrt(c[a] * 3.14159265358979323846) * (std::erf((1.0 - i) / q) - std::erf(-i / q));
+                if (correlated && !(k > 0.0 && std::isfinite(k)))
+                    return fail(r, CL2_E_STATE, "the camera's pixel sizes give no reconstruction weights");
+                (a == 0 ? K.kx : K.ky)[i + 1] = (float)k;
+            }
+    }
+    TRY(drain(r));
+    TRY(need_filter_buffers(r));
+    const int grid = std::min(grid_for(FB), ERR_BLOCKS);
+    if (!r->d_de_sum) {
+        int rc = dev_alloc(r, &r->d_de_y, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_de_a, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_de_yp, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_de_fy, 3 * FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_de_map, FB);
+        if (rc == CL2_OK) rc = dev_alloc(r, &r->d_de_sum, FB + (size_t)DE_SUMS * ERR_BLOCKS + 8);   // last: the set is complete
+        if (rc != CL2_OK) return rc;
+    }
+    double* const partial = r->d_de_sum + FB;
+    double* const res = partial + (size_t)DE_SUMS * ERR_BLOCKS;
+    hipStream_t st = r->stream;
+    auto passes = [&](const float4* src, float* dst) {
+        return kind == 0 ? denoise_passes(r, iterations, sigma, sigma_depth, sigma_albedo, src, dst)
+                         : guided_passes(r, iterations, sigma, sigma_depth, sigma_albedo, src, dst, nullptr);
+    };
+    hipLaunchKernelGGL(k_de_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, kind, (const float*)r->d_acc, (const float*)r->d_mom,
+                       r->d_de_y, r->d_de_a, iterations == 0 ? r->d_de_fy : (float*)nullptr);
+    HIP_TRY(r, hipGetLastError());
+    TRY(passes(r->d_de_y, r->d_de_fy));
+    HIP_TRY(r, hipMemsetAsync(r->d_de_sum, 0, FB * sizeof(double), st));
+    const double scale = ((double)epsilon * (double)epsilon) * (double)probes;
+    for (int k = 0; k < probes; k++) {
+        hipLaunchKernelGGL(k_de_perturb, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->W, r->H, seed + (uint32_t)k, epsilon, correlated, K,
+                           (const float4*)r->d_de_y, (const float4*)r->d_de_a, r->d_de_yp, iterations == 0 ? r->d_dn_out : (float*)nullptr);
+        HIP_TRY(r, hipGetLastError());
+        TRY(passes(r->d_de_yp, r->d_dn_out));
+        auto terms = [&](auto LAST) {
+            hipLaunchKernelGGL(k_de_terms<LAST.value != 0>, dim3(grid), dim3(256), 0, st, r->FB, (const float4*)r->d_de_y,
+                               (const float4*)r->d_de_yp, (const float*)r->d_de_fy, (const float*)r->d_dn_out, (const float4*)r->d_de_a,
+                               r->d_de_sum, scale, floor, r->d_de_map, partial);
+        };
+        if (k == probes - 1) terms(int_c<1>{}); else terms(int_c<0>{});
+        HIP_TRY(r, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_de_final, dim3(1), dim3(256), 0, st, (const double*)partial, grid, res);
+    HIP_TRY(r, hipGetLastError());
+    TRY(drain(r));
+    HIP_TRY(r, hipMemcpy(out, res, 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_map) HIP_TRY(r, hipMemcpy(out_map, r->d_de_map, FB * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_probe) {
+        // y' is a float4 buffer: its colours go out through d_de_fy, once F(y) has left it
+        HIP_TRY(r, hipMemcpy(out_probe + 3 * FB, r->d_de_fy, 3 * FB * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(r, hipMemcpy(out_probe + 6 * FB, r->d_dn_out, 3 * FB * sizeof(float), hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(k_de_pack, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float4*)r->d_de_yp, r->d_de_fy);
+        HIP_TRY(r, hipGetLastError());
+        HIP_TRY(r, hipStreamSynchronize(st));
+        HIP_TRY(r, hipMemcpy(out_probe, r->d_de_fy, 3 * FB * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return CL2_OK;
 }
 
 // ---------------------------------------------------------------- kept picture and its tone map (csrc/tonemap_picture.hpp)

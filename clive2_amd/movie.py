@@ -59,6 +59,10 @@ def main(argv=None):
     ap.add_argument("--error-floor", type=float, default=None,
                     help=f"floor of the relative error's denominator L + floor (default {ERROR_FLOOR})")
     ap.add_argument("--check-every", type=int, default=8, help="passes between two checks of --target-error")
+    ap.add_argument("--error-of", choices=("picture", "denoised"), default="picture",
+                    help="what --target-error measures: the raw Monte Carlo picture (Renderer.relative_error, the default) or, with "
+                         "--denoise, the filtered picture that is saved (Renderer.denoised_error, DESIGN.md 6.15; the guided filter's "
+                         "with --variance-guided).  Not with --adaptive, --robust or --robust-denoise")
     ap.add_argument("--adaptive", action="store_true",
                     help="with --target-error: spread the camera samples by the per-pixel error estimate before every check "
                          "(adaptive sampling, DESIGN.md 6.5)")
@@ -96,6 +100,11 @@ def main(argv=None):
         ap.error("--uniform-share must be in (0, 1]")
     if args.device_tonemap and args.host_tonemap:
         ap.error("--device-tonemap does not go with --host-tonemap")
+    if args.error_of == "denoised":
+        if args.target_error is None or not args.denoise:
+            ap.error("--error-of denoised measures the picture --denoise saves: it needs --target-error and --denoise")
+        if args.adaptive or args.robust or args.robust_denoise:
+            ap.error("--error-of denoised does not go with --adaptive, --robust or --robust-denoise")
 
     rank, local_rank, world = rank_info()
     out_dir = os.path.join(args.out_root, args.movie_name)
@@ -119,7 +128,13 @@ def main(argv=None):
             renderer.set_error_tracking(True)
         if args.robust or args.robust_denoise:
             renderer.set_robust_buckets(args.robust or args.robust_denoise)
-        if args.target_error is not None:
+        filtered = args.error_of == "denoised"
+        if filtered:
+            renderer.render_features(args.feature_samples)
+            _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every,
+                                               metric="guided" if args.variance_guided else "denoised")
+            note = f" ({renderer.samples} samples, e_dn of the denoised picture {reached:.4g})"
+        elif args.target_error is not None:
             _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every,
                                                adaptive=args.adaptive, uniform_share=args.uniform_share)
             note = f" ({renderer.samples} samples, relative error {reached:.4g})"
@@ -133,7 +148,8 @@ def main(argv=None):
             renderer.render_features(args.feature_samples)
             image = renderer.tone_mapped("robust_guided") if dev else renderer.robust_guided_image
         elif args.denoise:
-            renderer.render_features(args.feature_samples)
+            if not filtered:
+                renderer.render_features(args.feature_samples)
             if dev:
                 image = renderer.tone_mapped("guided" if args.variance_guided else "denoised")
             else:

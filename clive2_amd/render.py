@@ -5,6 +5,7 @@ instead of opening a cv2 window (display code is out of scope).
     python -m clive2_amd.render --scene empty --samples 4 --denoise --out cornell_denoised.png
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --error-out err.npy
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --denoise --variance-guided --out cornell_guided.png
+    python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --denoise --error-of denoised --out cornell_until_denoised.png
     python -m clive2_amd.render --scene empty --samples 256 --robust --out cornell_robust.png
     python -m clive2_amd.render --scene empty --samples 256 --robust-denoise --out cornell_robust_denoised.png
     python -m clive2_amd.render --scene empty --samples 64 --path-length 3: --out cornell_indirect_only.png
@@ -119,6 +120,10 @@ def main(argv=None):
     ap.add_argument("--error-floor", type=float, default=None,
                     help=f"floor of the relative error's denominator L + floor (default {ERROR_FLOOR})")
     ap.add_argument("--check-every", type=int, default=8, help="passes between two checks of --target-error")
+    ap.add_argument("--error-of", choices=("picture", "denoised"), default="picture",
+                    help="what --target-error measures: the raw Monte Carlo picture (Renderer.relative_error, the default) or, with "
+                         "--denoise, the filtered picture that is saved (Renderer.denoised_error, DESIGN.md 6.15; the guided filter's "
+                         "with --variance-guided).  Not with --adaptive, --robust or --robust-denoise")
     ap.add_argument("--adaptive", action="store_true",
                     help="with --target-error: spread the camera samples by the per-pixel error estimate before every check "
                          "(adaptive sampling, DESIGN.md 6.5)")
@@ -175,6 +180,11 @@ def main(argv=None):
         ap.error("--robust-denoise is a picture of its own: it does not go with --robust, --denoise or --variance-guided")
     if args.uniform_share is not None and not (0.0 < args.uniform_share <= 1.0):
         ap.error("--uniform-share must be in (0, 1]")
+    if args.error_of == "denoised":
+        if args.target_error is None or not args.denoise:
+            ap.error("--error-of denoised measures the picture --denoise saves: it needs --target-error and --denoise")
+        if args.adaptive or args.robust or args.robust_denoise:
+            ap.error("--error-of denoised does not go with --adaptive, --robust or --robust-denoise")
 
     if args.strategies is not None and args.path_length is not None:
         ap.error("--strategies and --path-length both set the strategy mask: give one")
@@ -236,8 +246,14 @@ def main(argv=None):
     t0 = time.time()
     failure = None
     reached = None
+    filtered = args.error_of == "denoised"
     try:
-        if args.target_error is not None:
+        if filtered:
+            renderer.render_features(args.feature_samples)
+            _, reached = renderer.render_until(args.target_error, max(1, -(-args.samples // K)), floor=args.error_floor,
+                                               check_every=args.check_every,
+                                               metric="guided" if args.variance_guided else "denoised")
+        elif args.target_error is not None:
             _, reached = renderer.render_until(args.target_error, max(1, -(-args.samples // K)), floor=args.error_floor,
                                                check_every=args.check_every, adaptive=args.adaptive,
                                                uniform_share=args.uniform_share)
@@ -266,7 +282,9 @@ def main(argv=None):
     dt = time.time() - t0
     rays = renderer.counters()["rays"]
     print(f"[rank {rank}] rendering took {dt:.2f} seconds ({renderer.samples} samples, {rays / max(dt, 1e-9) / 1e6:.0f} Mrays/s)")
-    if reached is not None:
+    if reached is not None and filtered:
+        print(f"[rank {rank}] target error {args.target_error}: {renderer.samples} samples, e_dn of the denoised picture {reached:.4g}")
+    elif reached is not None:
         print(f"[rank {rank}] target error {args.target_error}: {renderer.samples} samples, relative error {reached:.4g}")
     if args.error_out and rank == 0:
         np.save(args.error_out, renderer.standard_error())
@@ -286,7 +304,8 @@ def main(argv=None):
         print(f"[rank {rank}] features ({args.feature_samples} rays per pixel) and denoising took {time.time() - t1:.2f} seconds")
     elif args.denoise:
         t1 = time.time()
-        renderer.render_features(args.feature_samples)
+        if not filtered:
+            renderer.render_features(args.feature_samples)
         if dev:
             image = renderer.tone_mapped("guided" if args.variance_guided else "denoised")
         else:

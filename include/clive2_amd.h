@@ -502,6 +502,37 @@ int cl2_denoise_guided(cl2_renderer* r, int iterations, float sigma_luma, float 
                        size_t n_floats, float* out_var, size_t n_var);
 /* e(floor), floor >= 0 and finite */
 int cl2_relative_error(cl2_renderer* r, double floor, double* out);
+/* The error of the FILTERED picture (csrc/denoise_error.hpp): Monte-Carlo SURE, Stein's unbiased risk estimate with the
+ * filter's divergence taken from finite differences along `probes` random perturbations.  No reference counterpart: the reference has
+ * neither a filter nor an error estimate (src/renderer.py:293-316).  kind 0: the passes of cl2_denoise (sigma = sigma_color), kind 1:
+ * those of cl2_denoise_guided (sigma = sigma_luma), launched as those calls launch them.  Per pixel p, with err_pixel's state and
+ * float64 variances (cl2_read_standard_error) and y the float32 colour cl2_denoise filters:
+ *     v_p = (float) min(var_L, 2^100)    s_p = (float) sqrt(v_p)    d_p,c = (float)(se_c / luma(se)), 1 when luma(se) is not > 0 or
+ *     not finite    a_p,c = s_p d_p,c (0 where the pixel is uncovered or has n < 2)      -- rank-1 colour noise of luma variance v_p
+ *     b_q = sign bit of a hash of (pixel index q, seed + probe)      z = b (correlated 0), or b passed through the mean 3 x 3
+ *     reconstruction weights of a camera sample and normalised to E z^2 = 1 over the in-frame sources (correlated 1)
+ *     y' = y + (epsilon z) a   (float32)      u = luma(y') - luma(y)      g = luma(F(y')) - luma(F(y))            (float64)
+ *     div_p = sum_probes u g / (epsilon^2 probes)          sure_p = (luma(F(y)) - luma(y))^2 - v_p + 2 div_p
+ * out[8]: [0] e_dn = sqrt(max(0, [1] / N)), +inf when N = 0 or [3] > 0; [1] sum over estimated pixels of
+ * sure_p / (luma(F(y)_p) + floor)^2 (a sure_p of exactly 0 adds 0); [2] N = covered pixels; [3] covered pixels with n < 2;
+ * [4] sum sure_p; [5] sum of the fidelity terms; [6] sum v_p; [7] sum 2 div_p.  The sums are taken in a fixed order without atomics:
+ * the same bytes on every call.  e_dn(floor) is cl2_relative_error's e(floor) for the filtered picture; with iterations 0 and
+ * correlated 0 it is e(floor) up to the rounding of y + delta.
+ * out_map: NULL (n_map 0) or W*H floats: 0 uncovered, +inf with n < 2, else (float) sure_p -- noisy and possibly negative for a
+ * single probe; the totals are what is calibrated.  out_probe: NULL (n_probe 0) or 3*(3*W*H) floats that receive y', F(y) and
+ * F(y') of the LAST probe, (H, W, 3) each; F(y) is cl2_denoise's / cl2_denoise_guided's picture byte for byte.
+ * Limits: the weight 1 / (luma F + floor)^2 depends on the data (as e(floor)'s does); for kind 1 the guide variance is treated as a
+ * fixed parameter of the filter; the estimate is unbiased under its own noise model and badly off under the other one (DESIGN 6.15
+ * has both modes measured on real renders: at 64 x 48 independent signs give estimate / true error 0.88 .. 1.20; on the 1080p
+ * Cornell box, where the filter removes 98 % of the variance, the truth lies between the modes, independent signs run low -- e_dn
+ * by a factor of up to 1.6 -- and for kind 1 the total is negative).
+ * Arguments: iterations and sigmas as the filter's own call checks them; probes 1..16; epsilon > 0 and finite (the Python binding:
+ * 1/16); correlated 0 or 1; floor >= 0 and finite; else CL2_E_INVALID.  CL2_E_STATE without current features, with error tracking off
+ * or with invalid moments.  Touches neither seeds, accumulators, moments, counters, a kept picture nor the guide variance of the
+ * last cl2_denoise_guided. */
+int cl2_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, float sigma_depth, float sigma_albedo, int probes,
+                      float epsilon, int correlated, uint32_t seed, double floor, double* out, float* out_map, size_t n_map,
+                      float* out_probe, size_t n_probe);
 /* Renders until e(floor) <= target.  Units are passes, as for cl2_run_samples(n): first min_passes, then chunks of check_every
  * (the last one clipped to max_passes), each through cl2_run_samples; after each chunk e(floor) is evaluated on the device, and
  * the call stops at the first chunk boundary with e <= target, or at max_passes.  *passes_done = passes rendered (also when the
