@@ -20,20 +20,8 @@ from clive2_amd.renderer import Renderer, make_seeds
 from oracle import oracle as orc
 
 
-_FLOAT_FIELDS = ("origin", "direction", "inv_direction", "color", "normal", "c_importance", "l_importance", "tot_importance")
-
-
-def canonical_nans(paths):
-    """A copy of a Path[] array with every NaN of its float fields in ONE bit pattern.  A NaN that both sides compute in the same
-    place (a reverse pdf of 0 / 0 at a grazing vertex: 3 scenes in 9,000, round 6) is the same result; its sign and payload are the
-    hardware's default for an invalid operation -- 0x7fc00000 on the GPU, 0xffc00000 ("real indefinite") on the x86 host of the oracle,
-    whatever Metal's is on the reference's GPU -- and say nothing about the computation."""
-    out = paths.copy()
-    rays = out["rays"]
-    for f in _FLOAT_FIELDS:
-        a = rays[f]
-        a[np.isnan(a)] = np.float32(np.nan)
-    return out
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from path_compare import canonical_nans                 # noqa: E402 (moved to the tests' helper; behaviour unchanged)
 
 
 def random_scene(rng, max_members=None):
