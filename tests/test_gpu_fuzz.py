@@ -1,5 +1,7 @@
 """Differential fuzzing in the GPU suite: a dozen random scenes (camera pose, meshes, all material types,
-odd frame sizes, both BVH builders, every launch organisation) -- HIP path vs oracle, bit for bit.
+odd frame sizes, both BVH builders, every launch organisation) -- HIP path vs oracle, bit for bit; and six more with lamps of
+emitter materials of every type and other camera films (random_scene(emitters=...): 20 to 400 extra emitters; wide, rolled and
+plain films on these seeds).
 The full run (`python tools/fuzz_parity.py 150`) is logged in profiles/r01_fuzz_parity.log."""
 import importlib.util
 import os
@@ -20,10 +22,21 @@ def _load_tool():
 
 @pytest.mark.parametrize("seed", list(range(500, 512)))
 def test_random_scene_matches_oracle(seed, oracle_mod):
+    _random_scene_matches_oracle(seed, oracle_mod, False)
+
+
+@pytest.mark.parametrize("seed", list(range(600, 606)))
+def test_random_scene_with_lamps_and_films_matches_oracle(seed, oracle_mod):
+    """The same with random_scene(emitters=...): 0-3 lamps of emitter materials of every type and one of four films, drawn from a
+    generator of their own."""
+    _random_scene_matches_oracle(seed, oracle_mod, np.random.RandomState(7000 + seed))
+
+
+def _random_scene_matches_oracle(seed, oracle_mod, emitters):
     from clive2_amd.renderer import Renderer, make_seeds
     fz = _load_tool()
     rng = np.random.RandomState(1000 + seed)
-    scene, desc = fz.random_scene(rng)
+    scene, desc = fz.random_scene(rng, emitters=emitters)
     B = scene.pixel_width * scene.pixel_height
     seeds = make_seeds(B, seed=seed)
     r, o = Renderer(scene, seeds=seeds), oracle_mod.OracleRenderer(scene, seeds=seeds)

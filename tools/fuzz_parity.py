@@ -1,7 +1,8 @@
 """Differential fuzzing: random scenes (camera pose, meshes, materials, frame size, launch organisation)
 rendered by the HIP path and by the oracle; subpaths, RNG state and filter aggregators must match bit for
-bit, the accumulated image to 5e-5.   python tools/fuzz_parity.py [--masked] [n_scenes] [first_seed]
---masked: strategy masks and layer tables against the masked oracle instead (masked_main)."""
+bit, the accumulated image to 5e-5.   python tools/fuzz_parity.py [--masked] [--emitters] [n_scenes] [first_seed]
+--masked: strategy masks and layer tables against the masked oracle instead (masked_main).
+--emitters: every scene with random_scene(emitters=RandomState(7000 + k)): extra lamps, emitter materials and a film."""
 import os
 import sys
 import time
@@ -24,7 +25,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 from path_compare import canonical_nans                 # noqa: E402 (moved to the tests' helper; behaviour unchanged)
 
 
-def random_scene(rng, max_members=None):
+def random_scene(rng, max_members=None, emitters=False):
+    """`emitters`: False, or a RandomState of its own (a seed makes one) from which 0-3 extra lamps, the emission of materials 8..11
+    and the camera's film are drawn -- `rng` is drawn from exactly as without it, so every seed keeps its scene."""
     w, h = int(rng.randint(17, 120)), int(rng.randint(11, 80))
     mats = np.zeros(12, dtype=st.Material)
     mats[:8] = get_materials()
@@ -49,8 +52,43 @@ def random_scene(rng, max_members=None):
     if rng.rand() < 0.3:                    # an open scene: the emitter and a random subset of the walls
         box = triangles_for_box()
         room = [t for t in box if t.emitter or rng.rand() < 0.5]
+    if emitters is not False:
+        return emitter_scene(emitters if isinstance(emitters, np.random.RandomState) else np.random.RandomState(emitters), w, h, mats,
+                             specs, center, direction, str(builder), room, max_members)
     return (c2.create_scene(w, h, center, direction, file_specs=specs, materials=mats, bvh_builder=str(builder), room=room, max_members=max_members),
             (w, h, len(specs), str(builder), 'open' if room is not None else 'closed') + ((f"mm{max_members}",) if max_members else ()))
+
+
+FILMS = ("plain", "wide", "big", "rolled")
+EMISSIONS = ((4.0, 0.5, 0.0), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), (0.5, 2.0, 1.0))
+
+
+def emitter_scene(erng, w, h, mats, specs, center, direction, builder, room, max_members):
+    """random_scene(emitters=...): the scene drawn from `rng` with, drawn from `erng`, an emission for each of materials 8..11, 0-3
+    lamps (icospheres of subdivision 0-2 whose faces are emitters of materials 6, 8..11, one material a lamp or one a face) and a
+    film: plain (w / h x 1), 1.2 x 0.5, 3.0 x 2.5, or plain and rolled about the viewing direction.  Assembled by
+    tests/emitter_scenes.py: scene_around, which restates create_scene around a given Camera."""
+    import emitter_scenes as es
+    from clive2_amd.camera import Camera
+    from clive2_amd.load import Triangle
+    for m in range(8, 12):
+        mats["emission"][m, :3] = EMISSIONS[erng.randint(0, len(EMISSIONS))]
+    lamps = []
+    for _ in range(erng.randint(0, 4)):
+        v, f = icosphere(int(erng.randint(0, 3)), radius=float(erng.uniform(0.3, 1.2)),
+                         center=(erng.uniform(-6, 6), erng.uniform(0, 7), erng.uniform(-7, 3)))
+        choice = [6, 8, 9, 10, 11]
+        one = int(erng.choice(choice)) if erng.rand() < 0.5 else None
+        lamps += [Triangle(*v[face], material=one if one is not None else choice[k % 5], emitter=True) for k, face in enumerate(f)]
+    film = FILMS[erng.randint(0, len(FILMS))]
+    pw, ph = {"wide": (1.2, 0.5), "big": (3.0, 2.5)}.get(film, (w / h, 1))
+    cam = Camera(center=center, direction=direction, pixel_width=w, pixel_height=h, phys_width=pw, phys_height=ph)
+    if film == "rolled":
+        cam = es.rolled(cam, float(erng.uniform(-1.5, 1.5)))
+    enclosure = (triangles_for_box() if room is None else list(room)) + lamps
+    scene = es.scene_around(cam, enclosure, mats, builder, meshes=specs, max_members=max_members)
+    return scene, (w, h, len(specs), builder, 'open' if room is not None else 'closed', f"lamps{len(lamps)}", film) + \
+        ((f"mm{max_members}",) if max_members else ())
 
 
 def masked_main(n, first):
@@ -82,6 +120,9 @@ def main():
     masked = "--masked" in sys.argv
     if masked:
         sys.argv.remove("--masked")
+    with_emitters = "--emitters" in sys.argv
+    if with_emitters:
+        sys.argv.remove("--emitters")
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     if masked:
@@ -92,7 +133,8 @@ def main():
         rng = np.random.RandomState(1000 + k)
         # round 6: every fifth scene is built with another leaf size (create_scene(max_members=...): 4, 2 or 1 instead of the reference's 8;
         # taken from the scene number, not from the generator, so that the scenes themselves stay what earlier rounds rendered)
-        scene, desc = random_scene(rng, max_members=(4, 2, 1)[(k // 5) % 3] if k % 5 == 4 else None)
+        scene, desc = random_scene(rng, max_members=(4, 2, 1)[(k // 5) % 3] if k % 5 == 4 else None,
+                                   emitters=np.random.RandomState(7000 + k) if with_emitters else False)
         B = scene.pixel_width * scene.pixel_height
         mode, levels, stages = int(rng.randint(0, 6)), int(rng.randint(0, 7)), int(rng.randint(-1, 3))
         flags = 0
