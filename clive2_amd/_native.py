@@ -18,15 +18,17 @@ LIB_PATH = os.path.join(_PKG, "libclive2_amd.so")
 TEST_LIB_PATH = os.path.join(_PKG, "libclive2_amd_test.so")
 _MAIN_SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("renderer_api.hip", "bvh_builder_gpu.hip", "det_splat.hip")]
 _HEADER = os.path.join(os.path.dirname(_PKG), "include", "clive2_amd.h")
+# additions to the closed ABI-6 surface of clive2_amd.h (EXT_EXPORTS below)
+_EXT_HEADER = os.path.join(os.path.dirname(_PKG), "include", "clive2_amd_ext.h")
 
 
 _TEST_ONLY_SOURCES = [os.path.join(os.path.dirname(_PKG), "tests", "connect_resolve_wide.hpp")]
 
 
 def _sources(variant=None):
-    """Everything the translation unit includes: every file under csrc/ plus the public header (the test variant also
+    """Everything the translation unit includes: every file under csrc/ plus the public headers (the test variant also
     includes the cross-check resolve kernel that lives under tests/)."""
-    own = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")) + glob.glob(os.path.join(_PKG, "csrc", "*.hpp"))) + [_HEADER]
+    own = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")) + glob.glob(os.path.join(_PKG, "csrc", "*.hpp"))) + [_HEADER, _EXT_HEADER]
     return own + (_TEST_ONLY_SOURCES if variant == "test" else [])
 
 # -ffp-contract=off / no fast-math: every float op of the kernels rounds once, in source order.
@@ -103,6 +105,9 @@ EXPORTS = [
     "cl2_wide_stack_capacity",
     "cl2_denoise_error",
 ]
+
+# include/clive2_amd_ext.h: EXPORTS is the closed ABI-6 surface, later entry points are listed here
+EXT_EXPORTS = ["cl2_ext_version", "cl2_denoise_select", "cl2_keep_selected_picture"]
 
 
 def _path(variant):
@@ -189,6 +194,12 @@ def lib(variant=None):
                                          C.c_void_p, C.c_size_t]
         L.cl2_denoise_error.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
                                         C.c_uint32, C.c_double, C.POINTER(C.c_double), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        L.cl2_ext_version.argtypes = []
+        L.cl2_denoise_select.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_uint32,
+                                         C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_double),
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        L.cl2_keep_selected_picture.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
+                                                C.c_uint32, C.c_int]
         L.cl2_set_error_tracking.argtypes = [C.c_void_p, C.c_int]
         L.cl2_get_error_tracking.argtypes = [C.c_void_p]
         L.cl2_read_moments_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]

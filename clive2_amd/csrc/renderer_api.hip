@@ -21,12 +21,14 @@
 #include <vector>
 
 #include "../../include/clive2_amd.h"
+#include "../../include/clive2_amd_ext.h"
 #include "kernels.hpp"
 #include "denoise.hpp"
 #include "denoise_error.hpp"
 #include "denoise_guided.hpp"
 #include "denoise_layers.hpp"
 #include "denoise_robust.hpp"
+#include "denoise_select.hpp"
 #include "error_estimate.hpp"
 #include "adaptive.hpp"
 #include "layers.hpp"
@@ -134,7 +136,7 @@ struct cl2_renderer {
     double* d_tone_partial = nullptr;  // device tone map: per-workgroup partial sums + the total (allocated by the first call)
     uint8_t* d_tone_out = nullptr;     // device tone map: the uint8 picture before it is copied out
     float* d_pic = nullptr;            // kept picture (cl2_keep_picture, tonemap_picture.hpp): (H, W, 3) b, g, r, allocated on first use
-    int pic_kind = 0;                  // ... 0 none, 1 denoised, 2 guided, 3 robust, 4 robust-guided, 5 loaded (cl2_write_picture), 6 layer, 7 sum of layers (cl2_keep_layer_picture)
+    int pic_kind = 0;                  // ... 0 none, 1 denoised, 2 guided, 3 robust, 4 robust-guided, 5 loaded (cl2_write_picture), 6 layer, 7 sum of layers (cl2_keep_layer_picture), 8 selected (cl2_keep_selected_picture)
     Stats* d_stats = nullptr;
     unsigned long long* d_block_stats = nullptr;   // [grid][4]: rays, box tests, tri tests, counted rays per workgroup slot
 
@@ -170,6 +172,15 @@ struct cl2_renderer {
     float* d_de_fy = nullptr;            // (H, W, 3) F(y); F(y') is the filters' d_dn_out
     float* d_de_map = nullptr;           // (H, W) the per-pixel estimate
     double* d_de_sum = nullptr;          // [W*H] sum over the probes of u g, then [DE_SUMS][ERR_BLOCKS] partials + [8] result
+    // the per-pixel choice among the fixed filter's scales (cl2_denoise_select, denoise_select.hpp), allocated by its first call
+    // and again when K grows
+    int ds_levels = 0;                   // K + 1 the buffers below are sized for; 0: none
+    float4* d_ds_lev = nullptr;          // [2][levels][W*H] L_j(y), then L_j(y') of the current probe
+    float4* d_ds_a = nullptr;            // A = (a, code) of k_de_input
+    double* d_ds_sum = nullptr;          // [levels][W*H] sums over the probes of u g_j, then [DE_SUMS][ERR_BLOCKS] partials + [8] result
+    float* d_ds_map = nullptr;           // [3][levels][W*H] m and the two buffers the smoothing passes alternate between
+    int* d_ds_scale = nullptr;           // (H, W) k*
+    float* d_ds_out = nullptr;           // (H, W, 3) the selected picture
 
     // error tracking (cl2_set_error_tracking, error_estimate.hpp): second moments of the addends, [8][W*H], while tracking is on
     float* d_mom = nullptr;
@@ -2976,6 +2987,175 @@ int cl2_keep_layer_picture(cl2_renderer* r, int layer, int iterations, const flo
     if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
     const int rc = run_denoise_layers(r, layer, iterations, sigma_color, sigma_depth, sigma_albedo, true, r->d_pic, nullptr, nullptr);
     if (rc == CL2_OK) r->pic_kind = layer < 0 ? 7 : 6;
+    else if (rc == CL2_E_HIP) r->pic_kind = 0;                    // launches may have written part of it
+    // every other refusal comes before the first launch: the previous picture stands; a buffer made for this call goes again
+    if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);
+    return rc;
+}
+
+// ---------------------------------------------------------------- the filter's scale per pixel (csrc/denoise_select.hpp, DESIGN 6.16;
+// declared in include/clive2_amd_ext.h)
+namespace {
+// buffers for K + 1 = `levels` candidates: kept while they are large enough, made again when K grows
+int need_select_buffers(cl2_renderer* r, int levels) {
+    if (r->ds_levels >= levels) return CL2_OK;
+    dev_free(r, r->d_ds_lev); dev_free(r, r->d_ds_a); dev_free(r, r->d_ds_sum); dev_free(r, r->d_ds_map);
+    dev_free(r, r->d_ds_scale); dev_free(r, r->d_ds_out);
+    r->ds_levels = 0;
+    const size_t FB = (size_t)r->FB, n = (size_t)levels * FB;
+    int rc = dev_alloc(r, &r->d_ds_lev, 2 * n);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_ds_a, FB);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_ds_sum, n + (size_t)DE_SUMS * ERR_BLOCKS + 8);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_ds_map, 3 * n);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_ds_scale, FB);
+    if (rc == CL2_OK) rc = dev_alloc(r, &r->d_ds_out, 3 * FB);
+    if (rc == CL2_OK) r->ds_levels = levels;                       // last: the set is complete
+    return rc;
+}
+
+// The checks that follow the callers' own (handle, outputs, sizes) and every launch, on drained streams; the picture goes to `dst`
+// (device memory; nullptr: d_ds_out).  Every refusal but CL2_E_NOMEM and CL2_E_HIP comes before the first allocation and launch.
+// *maps_out: where M lies (m is d_ds_map).  The buffers are laid out for r->ds_levels, the launches use K + 1 of them.
+int run_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes, float epsilon,
+               int correlated, uint32_t seed, int smooth_passes, double floor, float* dst, const float** maps_out) {
+    if (iterations < 1 || iterations > 12) return fail(r, CL2_E_INVALID, "scale selection: iterations must be in 1..12");
+    if (smooth_passes < 0 || smooth_passes > DS_MAX_SMOOTH) return fail(r, CL2_E_INVALID, "smooth_passes must be in 0..4");
+    if (probes < 1 || probes > 16) return fail(r, CL2_E_INVALID, "probes must be in 1..16");
+    if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return fail(r, CL2_E_INVALID, "epsilon must be positive and finite");
+    if (correlated < 0 || correlated > 1) return fail(r, CL2_E_INVALID, "correlated must be 0 or 1");
+    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
+    TRY(denoise_checks(r, iterations, sigma_color, sigma_depth, sigma_albedo));
+    TRY(need_moments(r));
+    // the mean reconstruction weights of a camera sample, as cl2_denoise_error forms them (denoise_error.hpp)
+    DeKernel K;
+    {
+        const float ppw = r->cam.phys_width / r->cam.pixel_width, pph = r->cam.phys_height / r->cam.pixel_height;
+        const double s2 = (double)ppw * ppw + (double)pph * pph;
+        const double c[2] = {s2 / (2.0 * ppw * ppw), s2 / (2.0 * pph * pph)};
+        for (int a = 0; a < 2; a++)
+            for (int i = -1; i <= 1; i++) {
+                const double q = std::sqrt(c[a]);
+                const double k = 0.5 * std::sqrt(c[a] * 3.14159265358979323846) * (std::erf((1.0 - i) / q) - std::erf(-i / q));
+                if (correlated && !(k > 0.0 && std::isfinite(k)))
+                    return fail(r, CL2_E_STATE, "the camera's pixel sizes give no reconstruction weights");
+                (a == 0 ? K.kx : K.ky)[i + 1] = (float)k;
+            }
+    }
+    TRY(drain(r));
+    const int levels = iterations + 1;
+    TRY(need_select_buffers(r, levels));
+    const size_t FB = (size_t)r->FB, n = (size_t)levels * FB;
+    float4* const L = r->d_ds_lev;
+    float4* const Lp = r->d_ds_lev + (size_t)r->ds_levels * FB;
+    double* const partial = r->d_ds_sum + (size_t)r->ds_levels * FB;
+    double* const res = partial + (size_t)DE_SUMS * ERR_BLOCKS;
+    float* const maps[3] = {r->d_ds_map, r->d_ds_map + (size_t)r->ds_levels * FB, r->d_ds_map + 2 * (size_t)r->ds_levels * FB};
+    if (!dst) dst = r->d_ds_out;
+    hipStream_t st = r->stream;
+    const dim3 tiles((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), tile(DN_TILE, DN_TILE);
+    const float den_a = sigma_albedo * sigma_albedo;
+    // denoise_passes' launches, every pass into the next level's float4 buffer
+    auto passes = [&](float4* lev) {
+        for (int i = 0; i < iterations; i++) {
+            const int step = 1 << i;
+            const float den_c = std::ldexp(sigma_color * sigma_color, -2 * i);
+            const float4* cin = lev + (size_t)i * FB;
+            float4* cout = lev + (size_t)(i + 1) * FB;
+            auto pass = [&](auto LDS_STEP) {
+                hipLaunchKernelGGL(k_denoise_pass<LDS_STEP.value>, tiles, tile, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin,
+                                   r->d_g0, r->d_g1, cout, (float*)nullptr);
+            };
+            if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
+            HIP_TRY(r, hipGetLastError());
+        }
+        return CL2_OK;
+    };
+    const int blocks = grid_for(FB);
+    hipLaunchKernelGGL(k_de_input, dim3(blocks), dim3(BLOCK), 0, st, r->FB, 0, (const float*)r->d_acc, (const float*)r->d_mom, L,
+                       r->d_ds_a, (float*)nullptr);
+    HIP_TRY(r, hipGetLastError());
+    TRY(passes(L));
+    HIP_TRY(r, hipMemsetAsync(r->d_ds_sum, 0, n * sizeof(double), st));
+    for (int k = 0; k < probes; k++) {
+        hipLaunchKernelGGL(k_de_perturb, dim3(blocks), dim3(BLOCK), 0, st, r->W, r->H, seed + (uint32_t)k, epsilon, correlated, K,
+                           (const float4*)L, (const float4*)r->d_ds_a, Lp, (float*)nullptr);
+        HIP_TRY(r, hipGetLastError());
+        TRY(passes(Lp));
+        hipLaunchKernelGGL(k_ds_terms, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, st, r->FB, levels, (const float4*)L,
+                           (const float4*)Lp, r->d_ds_sum);
+        HIP_TRY(r, hipGetLastError());
+    }
+    const double scale = ((double)epsilon * (double)epsilon) * (double)probes;
+    hipLaunchKernelGGL(k_ds_map, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, st, r->FB, levels, (const float4*)L,
+                       (const float4*)r->d_ds_a, (const double*)r->d_ds_sum, scale, maps[0]);
+    HIP_TRY(r, hipGetLastError());
+    const float* M = maps[0];
+    for (int s = 0; s < smooth_passes; s++) {
+        float* const to = maps[1 + (s & 1)];
+        hipLaunchKernelGGL(k_ds_smooth, tiles, tile, 0, st, r->W, r->H, levels, 1 << s, sigma_depth, den_a, M, (const float4*)r->d_g0,
+                           (const float4*)r->d_g1, (const float4*)r->d_ds_a, to);
+        HIP_TRY(r, hipGetLastError());
+        M = to;
+    }
+    const int grid = std::min(blocks, ERR_BLOCKS);
+    hipLaunchKernelGGL(k_ds_select, dim3(grid), dim3(256), 0, st, r->FB, levels, (const float4*)L, (const float4*)r->d_ds_a, M, floor,
+                       r->d_ds_scale, dst, partial);
+    hipLaunchKernelGGL(k_de_final, dim3(1), dim3(256), 0, st, (const double*)partial, grid, res);
+    HIP_TRY(r, hipGetLastError());
+    if (maps_out) *maps_out = M;
+    return drain(r);
+}
+}  // namespace
+
+int cl2_ext_version(void) { return 1; }
+
+int cl2_denoise_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
+                       float epsilon, int correlated, uint32_t seed, int smooth_passes, double floor, float* out_bgr, size_t n_floats,
+                       int32_t* out_scale, size_t n_scale, double* out, float* out_maps, size_t n_maps, float* out_levels,
+                       size_t n_levels) {
+    STAGE_PROLOGUE(r);
+    if (!out) return fail(r, CL2_E_INVALID, "NULL output");
+    if (iterations < 1 || iterations > 12) return fail(r, CL2_E_INVALID, "scale selection: iterations must be in 1..12");
+    const size_t FB = (size_t)r->FB, levels = (size_t)iterations + 1;
+    if (out_bgr ? n_floats != 3 * FB : n_floats != 0) return fail(r, CL2_E_INVALID, "the selected picture must hold 3*W*H floats (or be NULL with n_floats 0)");
+    if (out_scale ? n_scale != FB : n_scale != 0) return fail(r, CL2_E_INVALID, "the scale map must hold W*H int32 (or be NULL with n_scale 0)");
+    if (out_maps ? n_maps != 2 * levels * FB : n_maps != 0)
+        return fail(r, CL2_E_INVALID, "the maps must hold 2*(iterations+1)*W*H floats (or be NULL with n_maps 0)");
+    if (out_levels ? n_levels != 6 * levels * FB : n_levels != 0)
+        return fail(r, CL2_E_INVALID, "the levels must hold 2*(iterations+1)*3*W*H floats (or be NULL with n_levels 0)");
+    const float* M = nullptr;
+    TRY(run_select(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes, floor, nullptr, &M));
+    const double* res = r->d_ds_sum + (size_t)r->ds_levels * FB + (size_t)DE_SUMS * ERR_BLOCKS;
+    HIP_TRY(r, hipMemcpy(out, res, 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_bgr) HIP_TRY(r, hipMemcpy(out_bgr, r->d_ds_out, 3 * FB * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_scale) HIP_TRY(r, hipMemcpy(out_scale, r->d_ds_scale, FB * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_maps) {
+        HIP_TRY(r, hipMemcpy(out_maps, r->d_ds_map, levels * FB * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(r, hipMemcpy(out_maps + levels * FB, M, levels * FB * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (out_levels) {
+        // the levels are float4 buffers: their colours go out through d_ds_out, once the picture has left it
+        for (size_t k = 0; k < 2 * levels; k++) {
+            const float4* src = r->d_ds_lev + ((k / levels) * (size_t)r->ds_levels + k % levels) * FB;
+            hipLaunchKernelGGL(k_de_pack, dim3(grid_for(FB)), dim3(BLOCK), 0, r->stream, r->FB, src, r->d_ds_out);
+            HIP_TRY(r, hipGetLastError());
+            HIP_TRY(r, hipStreamSynchronize(r->stream));
+            HIP_TRY(r, hipMemcpy(out_levels + k * 3 * FB, r->d_ds_out, 3 * FB * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }
+    return CL2_OK;
+}
+
+int cl2_keep_selected_picture(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
+                              float epsilon, int correlated, uint32_t seed, int smooth_passes) {
+    STAGE_PROLOGUE(r);
+    TRY(drain(r));
+    const bool fresh = !r->d_pic;
+    if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
+    // the totals are formed with floor 0 and stay on the device: only the picture is kept
+    const int rc = run_select(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes, 0.0,
+                              r->d_pic, nullptr);
+    if (rc == CL2_OK) r->pic_kind = 8;
     else if (rc == CL2_E_HIP) r->pic_kind = 0;                    // launches may have written part of it
     // every other refusal comes before the first launch: the previous picture stands; a buffer made for this call goes again
     if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);

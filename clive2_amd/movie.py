@@ -54,6 +54,11 @@ def main(argv=None):
     ap.add_argument("--variance-guided", action="store_true",
                     help="with --denoise: the filter whose edge-stop follows the per-pixel error estimate (Renderer.guided_image, "
                          "DESIGN.md 6.6).  Turns error tracking on before each frame's first sample")
+    ap.add_argument("--select-scale", action="store_true",
+                    help="with --denoise: choose the filter's number of passes per pixel by smoothed SURE maps "
+                         "(Renderer.selected_image, DESIGN.md 6.16).  Turns error tracking on before each frame's first sample.  Goes "
+                         "with --target-error on the raw metric, --feature-samples and --device-tonemap; not with --variance-guided, "
+                         "--robust, --robust-denoise or --error-of denoised")
     ap.add_argument("--target-error", type=float, default=None,
                     help="render each frame until its relative error (Renderer.relative_error) is at most this, --samples as the cap")
     ap.add_argument("--error-floor", type=float, default=None,
@@ -88,6 +93,12 @@ def main(argv=None):
         ap.error("--adaptive needs --target-error")
     if args.variance_guided and not args.denoise:
         ap.error("--variance-guided needs --denoise")
+    if args.select_scale:
+        if not args.denoise:
+            ap.error("--select-scale needs --denoise")
+        if args.variance_guided or args.robust or args.robust_denoise or args.error_of == "denoised":
+            ap.error("--select-scale chooses among the passes of the fixed filter: it does not go with --variance-guided, --robust, "
+                     "--robust-denoise or --error-of denoised")
     if args.robust and not (3 <= args.robust <= 16):
         ap.error("--robust takes 3..16 buckets")
     if args.robust and args.denoise:
@@ -124,7 +135,7 @@ def main(argv=None):
                 raise
             renderer = Renderer(scene, device=0)     # the launcher exposes one GPU per rank: it is device 0
         note = ""
-        if args.variance_guided:
+        if args.variance_guided or args.select_scale:
             renderer.set_error_tracking(True)
         if args.robust or args.robust_denoise:
             renderer.set_robust_buckets(args.robust or args.robust_denoise)
@@ -150,7 +161,9 @@ def main(argv=None):
         elif args.denoise:
             if not filtered:
                 renderer.render_features(args.feature_samples)
-            if dev:
+            if args.select_scale:
+                image = renderer.tone_mapped("selected") if dev else renderer.selected_image
+            elif dev:
                 image = renderer.tone_mapped("guided" if args.variance_guided else "denoised")
             else:
                 image = renderer.guided_image if args.variance_guided else renderer.denoised_image

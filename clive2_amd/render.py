@@ -6,6 +6,7 @@ instead of opening a cv2 window (display code is out of scope).
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --error-out err.npy
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --denoise --variance-guided --out cornell_guided.png
     python -m clive2_amd.render --scene empty --target-error 0.05 --samples 1024 --denoise --error-of denoised --out cornell_until_denoised.png
+    python -m clive2_amd.render --scene empty --samples 64 --denoise --select-scale --scale-out passes.npy --out cornell_selected.png
     python -m clive2_amd.render --scene empty --samples 256 --robust --out cornell_robust.png
     python -m clive2_amd.render --scene empty --samples 256 --robust-denoise --out cornell_robust_denoised.png
     python -m clive2_amd.render --scene empty --samples 64 --path-length 3: --out cornell_indirect_only.png
@@ -114,6 +115,13 @@ def main(argv=None):
     ap.add_argument("--variance-guided", action="store_true",
                     help="with --denoise: the filter whose edge-stop follows the per-pixel error estimate (Renderer.guided_image, "
                          "DESIGN.md 6.6): it closes where the picture has converged.  Turns error tracking on before the first sample")
+    ap.add_argument("--select-scale", action="store_true",
+                    help="with --denoise: choose the filter's number of passes per pixel by smoothed SURE maps "
+                         "(Renderer.selected_image, DESIGN.md 6.16).  Turns error tracking on before the first sample.  Goes with "
+                         "--target-error on the raw metric, --feature-samples and --device-tonemap; not with --variance-guided, "
+                         "--robust, --robust-denoise, --denoise-layers or --error-of denoised")
+    ap.add_argument("--scale-out", type=str, default=None, metavar="PATH.npy",
+                    help="with --select-scale: save the chosen pass count per pixel ((H, W) int32) as .npy")
     ap.add_argument("--target-error", type=float, default=None,
                     help="render until the relative error e (Renderer.relative_error) is at most this, with --samples as the cap "
                          "(one rank only)")
@@ -170,6 +178,14 @@ def main(argv=None):
         ap.error("--adaptive needs --target-error")
     if args.variance_guided and not args.denoise:
         ap.error("--variance-guided needs --denoise")
+    if args.select_scale:
+        if not args.denoise:
+            ap.error("--select-scale needs --denoise")
+        if args.variance_guided or args.robust or args.robust_denoise or args.denoise_layers or args.error_of == "denoised":
+            ap.error("--select-scale chooses among the passes of the fixed filter: it does not go with --variance-guided, --robust, "
+                     "--robust-denoise, --denoise-layers or --error-of denoised")
+    if args.scale_out and not args.select_scale:
+        ap.error("--scale-out saves the scale map of --select-scale")
     if args.robust and not (3 <= args.robust <= 16):
         ap.error("--robust takes 3..16 buckets")
     if args.robust and args.denoise:
@@ -229,7 +245,7 @@ def main(argv=None):
         renderer.set_reproducible(True)
     if args.visibility_query:
         renderer.set_connection_query(1)
-    if args.target_error is not None or args.error_out or args.variance_guided:
+    if args.target_error is not None or args.error_out or args.variance_guided or args.select_scale:
         renderer.set_error_tracking(True)
     if args.robust or args.robust_denoise:
         renderer.set_robust_buckets(args.robust or args.robust_denoise)
@@ -306,7 +322,11 @@ def main(argv=None):
         t1 = time.time()
         if not filtered:
             renderer.render_features(args.feature_samples)
-        if dev:
+        if args.select_scale:
+            if args.scale_out:
+                np.save(args.scale_out, renderer.selected_radiance(return_scale=True)[1])
+            image = renderer.tone_mapped("selected") if dev else renderer.selected_image
+        elif dev:
             image = renderer.tone_mapped("guided" if args.variance_guided else "denoised")
         else:
             image = renderer.guided_image if args.variance_guided else renderer.denoised_image

@@ -39,6 +39,14 @@ ERROR_FLOOR = 0.001
 # correlated; glass scene 1.04 / 1.20 independent and 0.58 / 0.44 correlated: the independent signs it is
 DENOISED_ERROR_CORRELATED = False
 
+# Default number of smoothing passes over the SURE maps of Renderer.selected_radiance: the smallest S in 0..4 for which, on 24 renders
+# of 32 samples at 64 x 48 against a 16,384-sample picture, the true squared luma error of the selected picture is not above the
+# larger of the raw picture's and the three-pass picture's, on the Cornell box and on the glass scene.  It holds for every S, so 0 it
+# is.  selected / raw / three passes, S = 0, 1, 2, 3, 4: Cornell box (6.0, 3.0, 2.6, 2.7, 3.1) / 8.7 / 71 x 1e-4, glass scene
+# (2.80, 3.08, 3.06, 3.06, 3.06) / 6.06 / 3.54 x 1e-2: two passes halve the Cornell box's error and cost the glass
+# scene 9 %
+SELECT_SMOOTH_PASSES = 0
+
 # Default uniform share beta of adaptive sampling's density m = beta + (1 - beta) r / mean(r) (Renderer.update_sample_density,
 # DESIGN.md 6.5)
 UNIFORM_SHARE = 0.25
@@ -258,7 +266,11 @@ class Renderer:
 
         `which` may also be "denoised", "guided", "robust" or "robust_guided": keep_picture(which) with the defaults, then
         tone_mapped_picture() -- the device counterpart of denoised_image, guided_image, robust_image and robust_guided_image.
-        This REPLACES the kept picture."""
+        "selected": keep_selected_picture() with the defaults, the counterpart of selected_image.  This REPLACES the kept picture."""
+        if which == "selected":                     # kept kind 8 has an entry point of its own (keep_selected_picture)
+            self._numpy2("tone_mapped()")
+            self.keep_selected_picture()
+            return self.tone_mapped_picture(exposure, white_point, log_average)
         if which in self._KEPT_KINDS:
             self._numpy2("tone_mapped()")
             self.keep_picture(which)
@@ -280,7 +292,8 @@ class Renderer:
 
     # ---- a kept picture and its tone map on the device (cl2_keep_picture ... cl2_picture_tone_map, csrc/tonemap_picture.hpp) ----
     _KEPT_KINDS = {"denoised": 1, "guided": 2, "robust": 3, "robust_guided": 4}
-    _KEPT_NAMES = {0: None, 1: "denoised", 2: "guided", 3: "robust", 4: "robust_guided", 5: "loaded", 6: "layer", 7: "layer_sum"}
+    _KEPT_NAMES = {0: None, 1: "denoised", 2: "guided", 3: "robust", 4: "robust_guided", 5: "loaded", 6: "layer", 7: "layer_sum",
+                   8: "selected"}
 
     @staticmethod
     def _numpy2(what):
@@ -315,7 +328,7 @@ class Renderer:
     @property
     def kept_kind(self):
         """what the handle keeps: None, "denoised", "guided", "robust", "robust_guided", "loaded" (load_picture), "layer" or "layer_sum"
-        (keep_layer_picture)"""
+        (keep_layer_picture), "selected" (keep_selected_picture)"""
         return self._KEPT_NAMES[int(self._L.cl2_kept_picture(self._h))]
 
     def kept_picture(self):
@@ -903,6 +916,67 @@ class Renderer:
         if return_probe:
             extras.append((probe[0], probe[1], probe[2]))
         return (float(out[0]), *extras) if extras else float(out[0])
+
+    # ---- the fixed filter's scale chosen per pixel (cl2_denoise_select, csrc/denoise_select.hpp) ----
+    def _select_args(self, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes):
+        d = self.DENOISE_DEFAULTS
+        return (d["iterations"] if iterations is None else int(iterations),
+                d["sigma_color"] if sigma_color is None else float(sigma_color),
+                d["sigma_depth"] if sigma_depth is None else float(sigma_depth),
+                d["sigma_albedo"] if sigma_albedo is None else float(sigma_albedo),
+                int(probes), float(epsilon), int(DENOISED_ERROR_CORRELATED if correlated is None else bool(correlated)),
+                C.c_uint32(int(seed) & 0xFFFFFFFF), SELECT_SMOOTH_PASSES if smooth_passes is None else int(smooth_passes))
+
+    def selected_radiance(self, iterations=None, sigma_color=None, sigma_depth=None, sigma_albedo=None, probes=1, epsilon=1 / 16,
+                          correlated=None, seed=0, smooth_passes=None, floor=None, return_scale=False, return_stats=False,
+                          return_maps=False):
+        """`radiance` after the fixed filter with the number of passes chosen PER PIXEL: float32 (H,W,3), BGR.  One run of
+        `iterations` = K passes gives the pictures of denoised_radiance(iterations=0 .. K); denoised_error's Monte-Carlo SURE
+        (probes, epsilon, correlated, seed as there) gives a map of the squared luma error of each; the maps are smoothed by
+        `smooth_passes` passes of the filter's kernel under its normal, depth and albedo weights, and every pixel takes the level
+        whose smoothed estimate is smallest.  render_features() first, error tracking on since the last reset.  Unset arguments
+        take DENOISE_DEFAULTS, DENOISED_ERROR_CORRELATED and SELECT_SMOOTH_PASSES; `floor` (ERROR_FLOOR) enters the statistics only.
+        The extras follow the picture in this order: return_scale the chosen pass count k*, int32 (H,W); return_stats the eight
+        float64 totals of cl2_denoise_select -- [0] e_sel, [4] the summed estimate of the selected picture, [5] of the K-pass and
+        [6] of the raw picture, [7] the sum of k*; return_maps (m, M), the raw and the smoothed maps, float32 (K+1,H,W) each.
+        e_sel is BIASED LOW: it estimates the level that looked best, and a minimum over noisy estimates lies below the estimate
+        of any fixed level, on top of the calibration limits of denoised_error.  It is a diagnostic."""
+        a = self._select_args(iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes)
+        f = self.ERROR_FLOOR if floor is None else float(floor)
+        H, W = self.pixel_height, self.pixel_width
+        pic = np.empty((H, W, 3), np.float32)
+        scale = np.empty((H, W), np.int32) if return_scale else None
+        maps = np.empty((2, max(a[0], 0) + 1, H, W), np.float32) if return_maps else None
+        out = (C.c_double * 8)()
+        self._check(self._L.cl2_denoise_select(self._h, *a, f, ptr(pic), C.c_size_t(pic.size), ptr(scale),
+                                               C.c_size_t(0 if scale is None else scale.size), out, ptr(maps),
+                                               C.c_size_t(0 if maps is None else maps.size), None, C.c_size_t(0)), "cl2_denoise_select")
+        extras = []
+        if return_scale:
+            extras.append(scale)
+        if return_stats:
+            extras.append(np.array(out[:], np.float64))
+        if return_maps:
+            extras.append((maps[0], maps[1]))
+        return (pic, *extras) if extras else pic
+
+    @property
+    def selected_image(self):
+        """`image` of the selected radiance: tone_map(selected_radiance(), exposure=4.0) on the host, uint8 (H,W,3), BGR."""
+        return tone_map(self.selected_radiance(), exposure=4.0)
+
+    def keep_selected_picture(self, **params):
+        """selected_radiance(**params) KEPT in device memory (kind "selected") under keep_picture's rules: a snapshot, nothing is
+        copied to the host, a refused call leaves the previous kept picture.  `params`: iterations, sigma_color, sigma_depth,
+        sigma_albedo, probes, epsilon, correlated, seed, smooth_passes."""
+        names = ("iterations", "sigma_color", "sigma_depth", "sigma_albedo", "probes", "epsilon", "correlated", "seed", "smooth_passes")
+        unknown = sorted(set(params) - set(names))
+        if unknown:
+            raise TypeError(f"keep_selected_picture takes {sorted(names)}, not {unknown}")
+        d = dict(iterations=None, sigma_color=None, sigma_depth=None, sigma_albedo=None, probes=1, epsilon=1 / 16, correlated=None,
+                 seed=0, smooth_passes=None)
+        d.update(params)
+        self._check(self._L.cl2_keep_selected_picture(self._h, *self._select_args(**d)), "cl2_keep_selected_picture")
 
     def best_iterations(self, kind="denoised", candidates=range(0, 6), **params):
         """The pass count among `candidates` whose filtered picture denoised_error(kind, iterations=..., **params) estimates to be
