@@ -107,7 +107,11 @@ EXPORTS = [
 ]
 
 # include/clive2_amd_ext.h: EXPORTS is the closed ABI-6 surface, later entry points are listed here
-EXT_EXPORTS = ["cl2_ext_version", "cl2_denoise_select", "cl2_keep_selected_picture"]
+EXT_EXPORTS = ["cl2_ext_version", "cl2_denoise_select", "cl2_keep_selected_picture",
+               # the split noise model (cl2_ext_features bit 0; csrc/error_split.hpp)
+               "cl2_ext_features", "cl2_set_split_tracking", "cl2_get_split_tracking", "cl2_read_split_moments_packed",
+               "cl2_write_split_moments_packed", "cl2_light_share", "cl2_denoise_error_model", "cl2_denoise_select_model",
+               "cl2_keep_selected_picture_model"]
 
 
 def _path(variant):
@@ -200,6 +204,15 @@ def lib(variant=None):
                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         L.cl2_keep_selected_picture.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int,
                                                 C.c_uint32, C.c_int]
+        L.cl2_ext_features.argtypes = []
+        L.cl2_denoise_error_model.argtypes = L.cl2_denoise_error.argtypes
+        L.cl2_denoise_select_model.argtypes = L.cl2_denoise_select.argtypes
+        L.cl2_keep_selected_picture_model.argtypes = L.cl2_keep_selected_picture.argtypes
+        L.cl2_set_split_tracking.argtypes = [C.c_void_p, C.c_int]
+        L.cl2_get_split_tracking.argtypes = [C.c_void_p]
+        L.cl2_read_split_moments_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_write_split_moments_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.cl2_light_share.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)]
         L.cl2_set_error_tracking.argtypes = [C.c_void_p, C.c_int]
         L.cl2_get_error_tracking.argtypes = [C.c_void_p]
         L.cl2_read_moments_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]

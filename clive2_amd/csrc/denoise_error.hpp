@@ -67,6 +67,7 @@
 #include <hip/hip_runtime.h>
 #include "denoise_guided.hpp"
 #include "error_estimate.hpp"
+#include "error_split.hpp"
 
 namespace cl2 {
 
@@ -111,30 +112,52 @@ __device__ __forceinline__ float de_sign(uint32_t q, uint32_t t) {
     return (h >> 31) ? -1.0f : 1.0f;
 }
 
-// y' = y + (eps z) a; the up to nine signs of the correlated field are hashed here, there is no sign buffer
+// the correlated field of (p, t): the up to nine signs are hashed here, there is no sign buffer
+__device__ __forceinline__ float de_correlated_z(int W, int H, int p, uint32_t t, const DeKernel& K) {
+    const int x = p % W, y = p / W;
+    float num = 0.0f, den = 0.0f;
+#pragma unroll
+    for (int j = -1; j <= 1; j++) {
+#pragma unroll
+        for (int i = -1; i <= 1; i++) {
+            const int sx = x - i, sy = y - j;
+            if (sx < 0 || sx >= W || sy < 0 || sy >= H) continue;
+            const float k = K.ky[j + 1] * K.kx[i + 1];
+            num += k * de_sign((uint32_t)(sy * W + sx), t);
+            den += k * k;
+        }
+    }
+    return (float)((double)num / sqrt((double)den));
+}
+
+// y' = y + (eps z) a
 __global__ __launch_bounds__(BLOCK) void k_de_perturb(int W, int H, uint32_t t, float eps, int correlated, DeKernel K,
                                                       const float4* __restrict__ Y, const float4* __restrict__ A,
                                                       float4* __restrict__ Yp, float* __restrict__ out3) {
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= W * H) return;
-    float z;
-    if (!correlated) z = de_sign((uint32_t)p, t);
-    else {
-        const int x = p % W, y = p / W;
-        float num = 0.0f, den = 0.0f;
-#pragma unroll
-        for (int j = -1; j <= 1; j++) {
-#pragma unroll
-            for (int i = -1; i <= 1; i++) {
-                const int sx = x - i, sy = y - j;
-                if (sx < 0 || sx >= W || sy < 0 || sy >= H) continue;
-                const float k = K.ky[j + 1] * K.kx[i + 1];
-                num += k * de_sign((uint32_t)(sy * W + sx), t);
-                den += k * k;
-            }
-        }
-        z = (float)((double)num / sqrt((double)den));
-    }
+    const float z = correlated ? de_correlated_z(W, H, p, t, K) : de_sign((uint32_t)p, t);
+    const float4 y4 = Y[p], a = A[p];
+    const float ez = eps * z;
+    const float4 o = make_float4(y4.x + ez * a.x, y4.y + ez * a.y, y4.z + ez * a.z, y4.w);
+    Yp[p] = o;
+    if (out3) { out3[3 * (size_t)p] = o.x; out3[3 * (size_t)p + 1] = o.y; out3[3 * (size_t)p + 2] = o.z; }
+}
+
+// Noise model 2, "split" (error_split.hpp): z_p = cs_p zK_p + cl_p b'_p with zK the correlated field of (p, t)
+// above, b'_p = de_sign(p, t ^ 0xA5A5A5A5), cs = (float) sqrt(1.0 - (double) rho_p), cl = (float) sqrt((double) rho_p) from the
+// float32 rho_p of k_de_rho; z in float32.  E z^2 = 1 (the two fields are independent and each has E = 1), so Var y' = eps^2 v as
+// in the pure modes, and a pair p != q carries cs_p cs_q times the reconstruction covariance.  rho = 1 is the independent mode
+// with other signs; rho = 0 gives the correlated mode's bytes (0 * b' adds +-0 to zK).
+__global__ __launch_bounds__(BLOCK) void k_de_perturb_split(int W, int H, uint32_t t, float eps, DeKernel K,
+                                                            const float* __restrict__ rho, const float4* __restrict__ Y,
+                                                            const float4* __restrict__ A, float4* __restrict__ Yp,
+                                                            float* __restrict__ out3) {
+    const int p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= W * H) return;
+    const float r = rho[p];
+    const float cs = (float)sqrt(1.0 - (double)r), cl = (float)sqrt((double)r);
+    const float z = cs * de_correlated_z(W, H, p, t, K) + cl * de_sign((uint32_t)p, t ^ 0xA5A5A5A5u);
     const float4 y4 = Y[p], a = A[p];
     const float ez = eps * z;
     const float4 o = make_float4(y4.x + ez * a.x, y4.y + ez * a.y, y4.z + ez * a.z, y4.w);

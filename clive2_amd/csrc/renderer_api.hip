@@ -30,6 +30,7 @@
 #include "denoise_robust.hpp"
 #include "denoise_select.hpp"
 #include "error_estimate.hpp"
+#include "error_split.hpp"
 #include "adaptive.hpp"
 #include "layers.hpp"
 #include "tonemap.hpp"
@@ -187,6 +188,10 @@ struct cl2_renderer {
     bool mom_valid = false;              // every addend in the accumulators also went into the moments
     bool acc_clean = true;               // the accumulators hold nothing (cl2_create, cl2_reset_accumulators)
     double* d_err_partial = nullptr;     // frame metric: [3][ERR_BLOCKS] per-workgroup partials + [4] result (first call)
+    // split tracking (cl2_set_split_tracking, error_split.hpp): the camera and the light part of the luma moments, [6][W*H], while on
+    float* d_smom = nullptr;
+    bool smom_valid = false;             // every addend in the accumulators also went into the split rows (the rules of mom_valid)
+    float* d_de_rho = nullptr;           // (H, W) the light share of noise model 2 (k_de_rho), allocated by its first use
 
     // robust picture (cl2_set_robust_buckets, robust.hpp): M partial sums per pixel, [M][4][W*H], while the buckets are on
     float* d_bkt = nullptr;
@@ -841,6 +846,9 @@ template <class F> void launch_accumulating(cl2_renderer* r, F&& f) { with_flags
 int launch_accumulate(cl2_renderer* r, hipStream_t st) {
     Timed t(r, ST_ACCUMULATE, st);
     const dim3 grid(grid_for(r->FB)), block(BLOCK);
+    if (r->d_smom)                       // split tracking: before the kernel that zeroes the light image (error_split.hpp)
+        hipLaunchKernelGGL(k_split_moments_staged, grid, block, 0, st, r->FB, r->streams, (const float4*)r->d_finalized,
+                           (const float*)r->d_sample_w, (const float4*)r->d_light_image, r->d_smom);
     launch_accumulating(r, [&](auto MOM, auto BKT) {
         hipLaunchKernelGGL((k_accumulate<MOM.value, BKT.value>), grid, block, 0, st, r->FB, r->streams, r->d_finalized, r->d_sample_w,
                            r->d_light_image, r->d_uni, r->d_acc, r->d_mom, r->d_bkt, r->bkt_M);
@@ -854,6 +862,11 @@ int launch_accumulate(cl2_renderer* r, hipStream_t st) {
 int launch_finalize_accumulate(cl2_renderer* r, hipStream_t st, bool mapped = false, uint32_t pass = 0) {
     Timed t(r, ST_FINALIZE, st);
     const dim3 grid(grid_for(r->FB)), block(BLOCK);
+    if (r->d_smom) {                     // split tracking: before the kernel that zeroes the light image (error_split.hpp)
+        if (mapped) return fail(r, CL2_E_STATE, "split tracking has no mapped form (cl2_set_sample_density refuses it)");
+        hipLaunchKernelGGL(k_split_moments_fused, grid, block, 0, st, r->B, r->W, r->H, (const float*)r->d_agg,
+                           (const float4*)r->d_light_image, r->d_smom);
+    }
     launch_accumulating(r, [&](auto MOM, auto BKT) {
         if (mapped)
             hipLaunchKernelGGL((k_finalize_accumulate_mapped<MOM.value, BKT.value>), grid, block, 0, st, r->B, r->W, r->H, r->d_agg,
@@ -1427,16 +1440,18 @@ int cl2_read_accumulators(cl2_renderer* r, float* img, float* wts, int32_t* coun
 }
 
 namespace {
-// The side sums of the accumulators: moments (error_estimate.hpp), buckets (robust.hpp) and layer accumulators (layers.hpp).  Each
+// The side sums of the accumulators: moments (error_estimate.hpp), buckets (robust.hpp), layer accumulators (layers.hpp) and split
+// rows (error_split.hpp).  Each
 // is a float array that exists while its feature is on, and a flag: every addend in the accumulators also went into the side sum.
 // The rules of that flag, for all of them:
 //   switched on           valid if the accumulators hold nothing yet (side_sum_on)
 //   cl2_reset_accumulators  zeroed, and valid if present (reset_side_sums)
 //   accumulators written by the caller  invalid (invalidate_side_sums) until the matching cl2_write_*_packed brings the side sum
 struct SideSum { float*& p; size_t n_floats; bool& valid; };
-inline std::array<SideSum, 3> side_sums(cl2_renderer* r) {
+inline std::array<SideSum, 4> side_sums(cl2_renderer* r) {
     const size_t FB = (size_t)r->FB;
-    return {{{r->d_mom, 8 * FB, r->mom_valid}, {r->d_bkt, 4 * (size_t)r->bkt_M * FB, r->bkt_valid}, {r->d_lacc, 3 * (size_t)r->n_layers * FB, r->lay_valid}}};
+    return {{{r->d_mom, 8 * FB, r->mom_valid}, {r->d_bkt, 4 * (size_t)r->bkt_M * FB, r->bkt_valid}, {r->d_lacc, 3 * (size_t)r->n_layers * FB, r->lay_valid},
+             {r->d_smom, (size_t)SPLIT_ROWS * FB, r->smom_valid}}};
 }
 int reset_side_sums(cl2_renderer* r) {
     for (SideSum& s : side_sums(r)) {
@@ -1696,6 +1711,7 @@ int cl2_reduce_accumulators(cl2_renderer* r) {
     r->acc_clean = false;
     r->mom_valid = t_min == 2.0;
     r->bkt_valid = bkt_agree && bm_min >= 1.0 && bv_min == 1.0;
+    r->smom_valid = false;               // the split rows are not reduced (error_split.hpp, DESIGN 6.17: a limit): cl2_reset_accumulators
     if (!bkt_agree)
         return fail(r, CL2_E_STATE, "the robust buckets are off on some ranks or differ in M: the accumulators were reduced, the buckets "
                                     "are invalid on every rank (cl2_reset_accumulators makes them valid again)");
@@ -2769,15 +2785,48 @@ int cl2_denoise_robust(cl2_renderer* r, int iterations, float sigma_luma, float 
 // The error estimate of the filtered picture (denoise_error.hpp): Monte-Carlo SURE over the passes of cl2_denoise
 // (kind 0) or cl2_denoise_guided (kind 1).  Reads accumulators, moments and features; writes its own buffers and the filters'
 // working buffers (d_dn[], d_dn_out); d_dn_var, a kept picture, seeds and counters are not touched.
-int cl2_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, float sigma_depth, float sigma_albedo, int probes,
-                      float epsilon, int correlated, uint32_t seed, double floor, double* out, float* out_map, size_t n_map,
+namespace {
+// the noise model of the SURE calls: 0 independent signs, 1 reconstruction-correlated, 2 split (error_split.hpp).  `legacy`: the call
+// came through an entry point that takes `correlated`, 0 or 1, and keeps its message
+int check_noise_model(cl2_renderer* r, int model, bool legacy) {
+    if (legacy) return (model < 0 || model > 1) ? fail(r, CL2_E_INVALID, "correlated must be 0 or 1") : CL2_OK;
+    return (model < 0 || model > 2) ? fail(r, CL2_E_INVALID, "noise_model must be 0 (independent), 1 (correlated) or 2 (split)") : CL2_OK;
+}
+int need_split_rows(cl2_renderer* r) {
+    if (!r->d_smom) return fail(r, CL2_E_STATE, "split tracking is off (cl2_set_split_tracking)");
+    if (!r->smom_valid)
+        return fail(r, CL2_E_STATE, "the split rows do not cover every sample in the accumulators (tracking was switched on after samples, "
+                                    "accumulators were written without them, or they were reduced over ranks): cl2_reset_accumulators or "
+                                    "cl2_write_split_moments_packed");
+    return CL2_OK;
+}
+// the light share of noise model 2 into d_de_rho, on `st`
+int launch_de_rho(cl2_renderer* r, hipStream_t st) {
+    hipLaunchKernelGGL(k_de_rho, dim3((unsigned)(((size_t)r->FB + 255) / 256)), dim3(256), 0, st, r->FB, (const float*)r->d_acc,
+                       (const float*)r->d_mom, (const float*)r->d_smom, r->d_de_rho);
+    HIP_TRY(r, hipGetLastError());
+    return CL2_OK;
+}
+// k_de_perturb, or k_de_perturb_split for model 2
+void launch_de_perturb(cl2_renderer* r, hipStream_t st, int model, uint32_t t, float eps, const DeKernel& K, const float4* Y,
+                       const float4* A, float4* Yp, float* out3) {
+    const dim3 grid(grid_for((size_t)r->FB)), block(BLOCK);
+    if (model == 2)
+        hipLaunchKernelGGL(k_de_perturb_split, grid, block, 0, st, r->W, r->H, t, eps, K, (const float*)r->d_de_rho, Y, A, Yp, out3);
+    else
+        hipLaunchKernelGGL(k_de_perturb, grid, block, 0, st, r->W, r->H, t, eps, model, K, Y, A, Yp, out3);
+}
+
+int run_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, float sigma_depth, float sigma_albedo, int probes,
+                      float epsilon, int model, bool legacy, uint32_t seed, double floor, double* out, float* out_map, size_t n_map,
                       float* out_probe, size_t n_probe) {
     STAGE_PROLOGUE(r);
     if (!out) return fail(r, CL2_E_INVALID, "NULL output");
     if (kind < 0 || kind > 1) return fail(r, CL2_E_INVALID, "denoise error: kind 0 (cl2_denoise) or 1 (cl2_denoise_guided)");
     if (probes < 1 || probes > 16) return fail(r, CL2_E_INVALID, "probes must be in 1..16");
     if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return fail(r, CL2_E_INVALID, "epsilon must be positive and finite");
-    if (correlated < 0 || correlated > 1) return fail(r, CL2_E_INVALID, "correlated must be 0 or 1");
+    TRY(check_noise_model(r, model, legacy));
+    const int correlated = model != 0;   // the reconstruction weights are needed
     if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
     const size_t FB = (size_t)r->FB;
     if (out_map ? n_map != FB : n_map != 0) return fail(r, CL2_E_INVALID, "the error map must hold W*H floats (or be NULL with n_map 0)");
@@ -2786,6 +2835,7 @@ int cl2_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, fl
     if (kind == 0) TRY(denoise_checks(r, iterations, sigma, sigma_depth, sigma_albedo));
     else TRY(guided_checks(r, iterations, sigma, sigma_depth, sigma_albedo));
     TRY(need_moments(r));
+    if (model == 2) TRY(need_split_rows(r));
     // the mean reconstruction weights of a camera sample, in float64 with erf (denoise_error.hpp)
     DeKernel K;
     {
@@ -2803,6 +2853,7 @@ int cl2_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, fl
     }
     TRY(drain(r));
     TRY(need_filter_buffers(r));
+    if (model == 2 && !r->d_de_rho) TRY(dev_alloc(r, &r->d_de_rho, FB));
     const int grid = std::min(grid_for(FB), ERR_BLOCKS);
     if (!r->d_de_sum) {
         int rc = dev_alloc(r, &r->d_de_y, FB);
@@ -2825,10 +2876,11 @@ int cl2_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, fl
     HIP_TRY(r, hipGetLastError());
     TRY(passes(r->d_de_y, r->d_de_fy));
     HIP_TRY(r, hipMemsetAsync(r->d_de_sum, 0, FB * sizeof(double), st));
+    if (model == 2) TRY(launch_de_rho(r, st));
     const double scale = ((double)epsilon * (double)epsilon) * (double)probes;
     for (int k = 0; k < probes; k++) {
-        hipLaunchKernelGGL(k_de_perturb, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->W, r->H, seed + (uint32_t)k, epsilon, correlated, K,
-                           (const float4*)r->d_de_y, (const float4*)r->d_de_a, r->d_de_yp, iterations == 0 ? r->d_dn_out : (float*)nullptr);
+        launch_de_perturb(r, st, model, seed + (uint32_t)k, epsilon, K, (const float4*)r->d_de_y, (const float4*)r->d_de_a, r->d_de_yp,
+                          iterations == 0 ? r->d_dn_out : (float*)nullptr);
         HIP_TRY(r, hipGetLastError());
         TRY(passes(r->d_de_yp, r->d_dn_out));
         auto terms = [&](auto LAST) {
@@ -2854,6 +2906,14 @@ int cl2_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, fl
         HIP_TRY(r, hipMemcpy(out_probe, r->d_de_fy, 3 * FB * sizeof(float), hipMemcpyDeviceToHost));
     }
     return CL2_OK;
+}
+}  // namespace
+
+int cl2_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, float sigma_depth, float sigma_albedo, int probes,
+                      float epsilon, int correlated, uint32_t seed, double floor, double* out, float* out_map, size_t n_map,
+                      float* out_probe, size_t n_probe) {
+    return run_denoise_error(r, kind, iterations, sigma, sigma_depth, sigma_albedo, probes, epsilon, correlated, true, seed, floor, out,
+                             out_map, n_map, out_probe, n_probe);
 }
 
 // ---------------------------------------------------------------- kept picture and its tone map (csrc/tonemap_picture.hpp)
@@ -3017,15 +3077,17 @@ int need_select_buffers(cl2_renderer* r, int levels) {
 // (device memory; nullptr: d_ds_out).  Every refusal but CL2_E_NOMEM and CL2_E_HIP comes before the first allocation and launch.
 // *maps_out: where M lies (m is d_ds_map).  The buffers are laid out for r->ds_levels, the launches use K + 1 of them.
 int run_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes, float epsilon,
-               int correlated, uint32_t seed, int smooth_passes, double floor, float* dst, const float** maps_out) {
+               int model, bool legacy, uint32_t seed, int smooth_passes, double floor, float* dst, const float** maps_out) {
     if (iterations < 1 || iterations > 12) return fail(r, CL2_E_INVALID, "scale selection: iterations must be in 1..12");
     if (smooth_passes < 0 || smooth_passes > DS_MAX_SMOOTH) return fail(r, CL2_E_INVALID, "smooth_passes must be in 0..4");
     if (probes < 1 || probes > 16) return fail(r, CL2_E_INVALID, "probes must be in 1..16");
     if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return fail(r, CL2_E_INVALID, "epsilon must be positive and finite");
-    if (correlated < 0 || correlated > 1) return fail(r, CL2_E_INVALID, "correlated must be 0 or 1");
+    TRY(check_noise_model(r, model, legacy));
+    const int correlated = model != 0;   // the reconstruction weights are needed
     if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
     TRY(denoise_checks(r, iterations, sigma_color, sigma_depth, sigma_albedo));
     TRY(need_moments(r));
+    if (model == 2) TRY(need_split_rows(r));
     // the mean reconstruction weights of a camera sample, as cl2_denoise_error forms them (denoise_error.hpp)
     DeKernel K;
     {
@@ -3044,6 +3106,7 @@ int run_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_d
     TRY(drain(r));
     const int levels = iterations + 1;
     TRY(need_select_buffers(r, levels));
+    if (model == 2 && !r->d_de_rho) TRY(dev_alloc(r, &r->d_de_rho, (size_t)r->FB));
     const size_t FB = (size_t)r->FB, n = (size_t)levels * FB;
     float4* const L = r->d_ds_lev;
     float4* const Lp = r->d_ds_lev + (size_t)r->ds_levels * FB;
@@ -3076,9 +3139,9 @@ int run_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_d
     HIP_TRY(r, hipGetLastError());
     TRY(passes(L));
     HIP_TRY(r, hipMemsetAsync(r->d_ds_sum, 0, n * sizeof(double), st));
+    if (model == 2) TRY(launch_de_rho(r, st));
     for (int k = 0; k < probes; k++) {
-        hipLaunchKernelGGL(k_de_perturb, dim3(blocks), dim3(BLOCK), 0, st, r->W, r->H, seed + (uint32_t)k, epsilon, correlated, K,
-                           (const float4*)L, (const float4*)r->d_ds_a, Lp, (float*)nullptr);
+        launch_de_perturb(r, st, model, seed + (uint32_t)k, epsilon, K, (const float4*)L, (const float4*)r->d_ds_a, Lp, (float*)nullptr);
         HIP_TRY(r, hipGetLastError());
         TRY(passes(Lp));
         hipLaunchKernelGGL(k_ds_terms, dim3((unsigned)((FB + 255) / 256)), dim3(256), 0, st, r->FB, levels, (const float4*)L,
@@ -3109,10 +3172,11 @@ int run_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_d
 
 int cl2_ext_version(void) { return 1; }
 
-int cl2_denoise_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
-                       float epsilon, int correlated, uint32_t seed, int smooth_passes, double floor, float* out_bgr, size_t n_floats,
-                       int32_t* out_scale, size_t n_scale, double* out, float* out_maps, size_t n_maps, float* out_levels,
-                       size_t n_levels) {
+namespace {
+int denoise_select_call(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
+                        float epsilon, int model, bool legacy, uint32_t seed, int smooth_passes, double floor, float* out_bgr,
+                        size_t n_floats, int32_t* out_scale, size_t n_scale, double* out, float* out_maps, size_t n_maps,
+                        float* out_levels, size_t n_levels) {
     STAGE_PROLOGUE(r);
     if (!out) return fail(r, CL2_E_INVALID, "NULL output");
     if (iterations < 1 || iterations > 12) return fail(r, CL2_E_INVALID, "scale selection: iterations must be in 1..12");
@@ -3124,7 +3188,7 @@ int cl2_denoise_select(cl2_renderer* r, int iterations, float sigma_color, float
     if (out_levels ? n_levels != 6 * levels * FB : n_levels != 0)
         return fail(r, CL2_E_INVALID, "the levels must hold 2*(iterations+1)*3*W*H floats (or be NULL with n_levels 0)");
     const float* M = nullptr;
-    TRY(run_select(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes, floor, nullptr, &M));
+    TRY(run_select(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, model, legacy, seed, smooth_passes, floor, nullptr, &M));
     const double* res = r->d_ds_sum + (size_t)r->ds_levels * FB + (size_t)DE_SUMS * ERR_BLOCKS;
     HIP_TRY(r, hipMemcpy(out, res, 8 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_bgr) HIP_TRY(r, hipMemcpy(out_bgr, r->d_ds_out, 3 * FB * sizeof(float), hipMemcpyDeviceToHost));
@@ -3146,20 +3210,115 @@ int cl2_denoise_select(cl2_renderer* r, int iterations, float sigma_color, float
     return CL2_OK;
 }
 
-int cl2_keep_selected_picture(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
-                              float epsilon, int correlated, uint32_t seed, int smooth_passes) {
+int keep_selected_call(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
+                       float epsilon, int model, bool legacy, uint32_t seed, int smooth_passes) {
     STAGE_PROLOGUE(r);
     TRY(drain(r));
     const bool fresh = !r->d_pic;
     if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
     // the totals are formed with floor 0 and stay on the device: only the picture is kept
-    const int rc = run_select(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes, 0.0,
+    const int rc = run_select(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, model, legacy, seed, smooth_passes, 0.0,
                               r->d_pic, nullptr);
     if (rc == CL2_OK) r->pic_kind = 8;
     else if (rc == CL2_E_HIP) r->pic_kind = 0;                    // launches may have written part of it
     // every other refusal comes before the first launch: the previous picture stands; a buffer made for this call goes again
     if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);
     return rc;
+}
+}  // namespace
+
+int cl2_denoise_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
+                       float epsilon, int correlated, uint32_t seed, int smooth_passes, double floor, float* out_bgr, size_t n_floats,
+                       int32_t* out_scale, size_t n_scale, double* out, float* out_maps, size_t n_maps, float* out_levels,
+                       size_t n_levels) {
+    return denoise_select_call(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, true, seed,
+                               smooth_passes, floor, out_bgr, n_floats, out_scale, n_scale, out, out_maps, n_maps, out_levels, n_levels);
+}
+
+int cl2_keep_selected_picture(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
+                              float epsilon, int correlated, uint32_t seed, int smooth_passes) {
+    return keep_selected_call(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, true, seed, smooth_passes);
+}
+
+// ---------------------------------------------------------------- the split noise model (csrc/error_split.hpp; declared
+// in include/clive2_amd_ext.h)
+int cl2_ext_features(void) { return 1; }
+
+int cl2_denoise_error_model(cl2_renderer* r, int kind, int iterations, float sigma, float sigma_depth, float sigma_albedo, int probes,
+                            float epsilon, int noise_model, uint32_t seed, double floor, double* out, float* out_map, size_t n_map,
+                            float* out_probe, size_t n_probe) {
+    return run_denoise_error(r, kind, iterations, sigma, sigma_depth, sigma_albedo, probes, epsilon, noise_model, false, seed, floor, out,
+                             out_map, n_map, out_probe, n_probe);
+}
+
+int cl2_denoise_select_model(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, int probes,
+                             float epsilon, int noise_model, uint32_t seed, int smooth_passes, double floor, float* out_bgr,
+                             size_t n_floats, int32_t* out_scale, size_t n_scale, double* out, float* out_maps, size_t n_maps,
+                             float* out_levels, size_t n_levels) {
+    return denoise_select_call(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, noise_model, false, seed,
+                               smooth_passes, floor, out_bgr, n_floats, out_scale, n_scale, out, out_maps, n_maps, out_levels, n_levels);
+}
+
+int cl2_keep_selected_picture_model(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo,
+                                    int probes, float epsilon, int noise_model, uint32_t seed, int smooth_passes) {
+    return keep_selected_call(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, noise_model, false, seed,
+                              smooth_passes);
+}
+
+int cl2_set_split_tracking(cl2_renderer* r, int on) {
+    if (!r) return CL2_E_INVALID;
+    if (on != 0 && on != 1) return fail(r, CL2_E_INVALID, "split tracking: 0 off, 1 on");
+    if (on && r->density)
+        return fail(r, CL2_E_STATE, "split tracking and a sample density exclude each other (no mapped form): cl2_set_sample_density(NULL) first");
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    if (!on) {
+        dev_free(r, r->d_smom);
+        r->smom_valid = false;
+        return CL2_OK;
+    }
+    if (r->d_smom) return CL2_OK;
+    return side_sum_on(r, r->d_smom, (size_t)SPLIT_ROWS * (size_t)r->FB, r->smom_valid, "split rows");
+}
+
+int cl2_get_split_tracking(const cl2_renderer* r) { return r ? (r->d_smom ? 1 : 0) : CL2_E_INVALID; }
+
+int cl2_read_split_moments_packed(cl2_renderer* r, float* dst, size_t n_floats) {
+    if (!r || !dst) return CL2_E_INVALID;
+    if (n_floats != (size_t)SPLIT_ROWS * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed split moments hold 6*W*H floats");
+    TRY(need_split_rows(r));
+    return packed_copy(r, dst, r->d_smom, n_floats, hipMemcpyDeviceToHost);
+}
+
+int cl2_write_split_moments_packed(cl2_renderer* r, const float* src, size_t n_floats) {
+    if (!r || !src) return CL2_E_INVALID;
+    if (n_floats != (size_t)SPLIT_ROWS * (size_t)r->FB) return fail(r, CL2_E_INVALID, "packed split moments hold 6*W*H floats");
+    if (!r->d_smom) return fail(r, CL2_E_STATE, "split tracking is off (cl2_set_split_tracking)");
+    TRY(packed_copy(r, r->d_smom, src, n_floats, hipMemcpyHostToDevice));
+    r->smom_valid = true;
+    return CL2_OK;
+}
+
+int cl2_light_share(cl2_renderer* r, float* out_map, size_t n_map, double* out) {
+    if (!r || !out) return CL2_E_INVALID;
+    const size_t FB = (size_t)r->FB;
+    if (out_map ? n_map != FB : n_map != 0) return fail(r, CL2_E_INVALID, "the light-share map must hold W*H floats (or be NULL with n_map 0)");
+    TRY(need_moments(r));
+    TRY(need_split_rows(r));
+    HIP_TRY(r, hipSetDevice(r->device));
+    TRY(drain(r));
+    if (!r->d_err_partial) TRY(dev_alloc(r, &r->d_err_partial, (size_t)3 * ERR_BLOCKS + 4));
+    if (out_map && !r->d_de_rho) TRY(dev_alloc(r, &r->d_de_rho, FB));
+    const int grid = std::min(grid_for(FB), ERR_BLOCKS);
+    double* res = r->d_err_partial + 3 * ERR_BLOCKS;
+    hipLaunchKernelGGL(k_light_share_partial, dim3(grid), dim3(256), 0, r->stream, r->FB, (const float*)r->d_acc, (const float*)r->d_mom,
+                       (const float*)r->d_smom, out_map ? r->d_de_rho : (float*)nullptr, r->d_err_partial);
+    hipLaunchKernelGGL(k_light_share_final, dim3(1), dim3(256), 0, r->stream, (const double*)r->d_err_partial, grid, res);
+    HIP_TRY(r, hipGetLastError());
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipMemcpy(out, res, 4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_map) HIP_TRY(r, hipMemcpy(out_map, r->d_de_rho, FB * sizeof(float), hipMemcpyDeviceToHost));
+    return CL2_OK;
 }
 
 int cl2_write_picture(cl2_renderer* r, const float* bgr, size_t n_floats) {
@@ -3237,6 +3396,7 @@ int cl2_run_until(cl2_renderer* r, double target, double floor, int min_passes, 
     STAGE_PROLOGUE(r);
     TRY(need_moments(r));
     if (r->adaptive) TRY(no_comm(r));
+    if (r->adaptive && r->d_smom) return fail(r, CL2_E_STATE, "adaptive sampling and split tracking exclude each other (no mapped form): cl2_set_split_tracking(0) first");
     int done = 0;
     double e = std::numeric_limits<double>::infinity();
     bool evaluated = false;
@@ -3265,6 +3425,7 @@ int cl2_set_sample_density(cl2_renderer* r, const float* density, size_t n) {
     if (!r) return CL2_E_INVALID;
     TRY(no_comm(r));
     if (density && r->n_layers > 0) return fail(r, CL2_E_STATE, "a sample density and layer accumulators exclude each other (no mapped form): cl2_set_layers(NULL, 0) first");
+    if (density && r->d_smom) return fail(r, CL2_E_STATE, "a sample density and split tracking exclude each other (no mapped form): cl2_set_split_tracking(0) first");
     if (density) {
         if (n != (size_t)r->FB) return fail(r, CL2_E_INVALID, "the density holds W*H weights");
         for (size_t i = 0; i < n; i++)
@@ -3296,6 +3457,7 @@ int cl2_update_sample_density(cl2_renderer* r, double floor, double uniform_shar
     if (!(uniform_share > 0.0 && uniform_share <= 1.0)) return fail(r, CL2_E_INVALID, "uniform_share must be in (0, 1]");
     TRY(no_comm(r));
     if (r->n_layers > 0) return fail(r, CL2_E_STATE, "a sample density and layer accumulators exclude each other (no mapped form): cl2_set_layers(NULL, 0) first");
+    if (r->d_smom) return fail(r, CL2_E_STATE, "a sample density and split tracking exclude each other (no mapped form): cl2_set_split_tracking(0) first");
     TRY(need_moments(r));
     HIP_TRY(r, hipSetDevice(r->device));
     TRY(drain(r));

@@ -16,6 +16,7 @@ import time
 import numpy as np
 
 from .distributed import rank_info
+from .render import _selected_image
 from .renderer import ERROR_FLOOR, UNIFORM_SHARE, Renderer, RendererError
 from .scene import create_scene_from_preset_with_params
 
@@ -59,6 +60,11 @@ def main(argv=None):
                          "(Renderer.selected_image, DESIGN.md 6.16).  Turns error tracking on before each frame's first sample.  Goes "
                          "with --target-error on the raw metric, --feature-samples and --device-tonemap; not with --variance-guided, "
                          "--robust, --robust-denoise or --error-of denoised")
+    ap.add_argument("--noise-model", choices=("independent", "correlated", "split"), default=None,
+                    help="the noise model of the SURE estimates behind --error-of denoised and --select-scale (needs --denoise and one of "
+                         "them; default independent): independent signs, signs spread like a camera sample over 3 x 3 pixels, or "
+                         "split -- a mix of the two by each pixel's light share (DESIGN.md 6.17), which turns split tracking on "
+                         "before the first sample and does not go with --adaptive")
     ap.add_argument("--target-error", type=float, default=None,
                     help="render each frame until its relative error (Renderer.relative_error) is at most this, --samples as the cap")
     ap.add_argument("--error-floor", type=float, default=None,
@@ -99,6 +105,11 @@ def main(argv=None):
         if args.variance_guided or args.robust or args.robust_denoise or args.error_of == "denoised":
             ap.error("--select-scale chooses among the passes of the fixed filter: it does not go with --variance-guided, --robust, "
                      "--robust-denoise or --error-of denoised")
+    if args.noise_model is not None:
+        if not (args.denoise and (args.error_of == "denoised" or args.select_scale)):
+            ap.error("--noise-model sets the noise model of --error-of denoised or --select-scale: it needs --denoise and one of them")
+        if args.noise_model == "split" and args.adaptive:
+            ap.error("--noise-model split does not go with --adaptive: a sample density has no split form")
     if args.robust and not (3 <= args.robust <= 16):
         ap.error("--robust takes 3..16 buckets")
     if args.robust and args.denoise:
@@ -137,13 +148,16 @@ def main(argv=None):
         note = ""
         if args.variance_guided or args.select_scale:
             renderer.set_error_tracking(True)
+        if args.noise_model == "split":
+            renderer.set_split_tracking(True)
         if args.robust or args.robust_denoise:
             renderer.set_robust_buckets(args.robust or args.robust_denoise)
         filtered = args.error_of == "denoised"
         if filtered:
             renderer.render_features(args.feature_samples)
             _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every,
-                                               metric="guided" if args.variance_guided else "denoised")
+                                               metric="guided" if args.variance_guided else "denoised",
+                                               filter_params=dict(noise=args.noise_model) if args.noise_model else None)
             note = f" ({renderer.samples} samples, e_dn of the denoised picture {reached:.4g})"
         elif args.target_error is not None:
             _, reached = renderer.render_until(args.target_error, args.samples, floor=args.error_floor, check_every=args.check_every,
@@ -162,7 +176,7 @@ def main(argv=None):
             if not filtered:
                 renderer.render_features(args.feature_samples)
             if args.select_scale:
-                image = renderer.tone_mapped("selected") if dev else renderer.selected_image
+                image = _selected_image(renderer, dev, args.noise_model)
             elif dev:
                 image = renderer.tone_mapped("guided" if args.variance_guided else "denoised")
             else:

@@ -38,6 +38,16 @@ def _save(path, image):
         np.save(path + ".npy", image)
 
 
+def _selected_image(renderer, dev, noise):
+    """--select-scale's picture under the noise model `noise` (None: the default), tone-mapped on the device or on the host"""
+    if noise is None:
+        return renderer.tone_mapped("selected") if dev else renderer.selected_image
+    if dev:
+        renderer.keep_selected_picture(noise=noise)
+        return renderer.tone_mapped_picture()
+    return tone_map(renderer.selected_radiance(noise=noise), exposure=4.0)
+
+
 def _write_layers(renderer, args, K):
     """--layers: the three layer pictures, tone-mapped with the log-average of their SUM so that their brightness is comparable."""
     t0 = time.time()
@@ -122,6 +132,14 @@ def main(argv=None):
                          "--robust, --robust-denoise, --denoise-layers or --error-of denoised")
     ap.add_argument("--scale-out", type=str, default=None, metavar="PATH.npy",
                     help="with --select-scale: save the chosen pass count per pixel ((H, W) int32) as .npy")
+    ap.add_argument("--noise-model", choices=("independent", "correlated", "split"), default=None,
+                    help="the noise model of the SURE estimates behind --error-of denoised and --select-scale (needs --denoise and one of "
+                         "them; default independent): independent signs, signs spread like a camera sample over 3 x 3 pixels, or "
+                         "split -- a mix of the two by each pixel's light share (DESIGN.md 6.17), which turns split tracking on "
+                         "before the first sample and does not go with --adaptive")
+    ap.add_argument("--light-share-out", type=str, default=None, metavar="PATH.npy",
+                    help="with --noise-model split: save each pixel's light share of the luma variance (Renderer.light_share: (H, W) "
+                         "float32, 1 where a pixel has no usable split) as .npy")
     ap.add_argument("--target-error", type=float, default=None,
                     help="render until the relative error e (Renderer.relative_error) is at most this, with --samples as the cap "
                          "(one rank only)")
@@ -186,6 +204,13 @@ def main(argv=None):
                      "--robust-denoise, --denoise-layers or --error-of denoised")
     if args.scale_out and not args.select_scale:
         ap.error("--scale-out saves the scale map of --select-scale")
+    if args.noise_model is not None:
+        if not (args.denoise and (args.error_of == "denoised" or args.select_scale)):
+            ap.error("--noise-model sets the noise model of --error-of denoised or --select-scale: it needs --denoise and one of them")
+        if args.noise_model == "split" and args.adaptive:
+            ap.error("--noise-model split does not go with --adaptive: a sample density has no split form")
+    if args.light_share_out and args.noise_model != "split":
+        ap.error("--light-share-out saves the light share of --noise-model split")
     if args.robust and not (3 <= args.robust <= 16):
         ap.error("--robust takes 3..16 buckets")
     if args.robust and args.denoise:
@@ -247,6 +272,8 @@ def main(argv=None):
         renderer.set_connection_query(1)
     if args.target_error is not None or args.error_out or args.variance_guided or args.select_scale:
         renderer.set_error_tracking(True)
+    if args.noise_model == "split":
+        renderer.set_split_tracking(True)
     if args.robust or args.robust_denoise:
         renderer.set_robust_buckets(args.robust or args.robust_denoise)
     if strategy_mask is not None:
@@ -268,7 +295,8 @@ def main(argv=None):
             renderer.render_features(args.feature_samples)
             _, reached = renderer.render_until(args.target_error, max(1, -(-args.samples // K)), floor=args.error_floor,
                                                check_every=args.check_every,
-                                               metric="guided" if args.variance_guided else "denoised")
+                                               metric="guided" if args.variance_guided else "denoised",
+                                               filter_params=dict(noise=args.noise_model) if args.noise_model else None)
         elif args.target_error is not None:
             _, reached = renderer.render_until(args.target_error, max(1, -(-args.samples // K)), floor=args.error_floor,
                                                check_every=args.check_every, adaptive=args.adaptive,
@@ -304,6 +332,10 @@ def main(argv=None):
         print(f"[rank {rank}] target error {args.target_error}: {renderer.samples} samples, relative error {reached:.4g}")
     if args.error_out and rank == 0:
         np.save(args.error_out, renderer.standard_error())
+    if args.light_share_out and rank == 0:
+        share, rho = renderer.light_share(return_map=True)
+        print(f"[rank {rank}] light share of the frame's luma variance {share:.4g}")
+        np.save(args.light_share_out, rho)
     if rank != 0:
         renderer.close()
         return 0
@@ -324,8 +356,8 @@ def main(argv=None):
             renderer.render_features(args.feature_samples)
         if args.select_scale:
             if args.scale_out:
-                np.save(args.scale_out, renderer.selected_radiance(return_scale=True)[1])
-            image = renderer.tone_mapped("selected") if dev else renderer.selected_image
+                np.save(args.scale_out, renderer.selected_radiance(return_scale=True, noise=args.noise_model)[1])
+            image = _selected_image(renderer, dev, args.noise_model)
         elif dev:
             image = renderer.tone_mapped("guided" if args.variance_guided else "denoised")
         else:

@@ -876,18 +876,66 @@ class Renderer:
         self._check(self._L.cl2_relative_error(self._h, f, C.byref(e)), "cl2_relative_error")
         return e.value
 
+    # ---- the luma variance split into its camera and its light part (cl2_set_split_tracking ... cl2_light_share,
+    # csrc/error_split.hpp) ----
+    def set_split_tracking(self, on=True):
+        """Keep every sample's luma moments apart for its camera part and its light part (off by default; 24*W*H bytes of device
+        memory while on), for noise="split" and light_share().  Turns error tracking on too if it is off.  The rules are those of
+        set_error_tracking: turned on while the accumulators hold samples, the rows stay invalid until reset_accumulators().
+        Not together with a sample density."""
+        if on and not self.error_tracking:
+            self.set_error_tracking(True)
+        self._check(self._L.cl2_set_split_tracking(self._h, int(bool(on))), "cl2_set_split_tracking")
+
+    @property
+    def split_tracking(self):
+        return bool(self._L.cl2_get_split_tracking(self._h) == 1)
+
+    def split_moments(self):
+        """The split rows [6][W*H] float32 (camera yc^2, yc wc, wc^2 | light yl^2, yl wl, wl^2), packed like moments()."""
+        a = np.empty(6 * self.batch_size, np.float32)
+        self._check(self._L.cl2_read_split_moments_packed(self._h, ptr(a), C.c_size_t(a.size)), "cl2_read_split_moments_packed")
+        return a
+
+    def load_split_moments(self, a):
+        """Write the split rows (checkpoints: after load_packed_accumulators, which invalidates them)."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        self._check(self._L.cl2_write_split_moments_packed(self._h, ptr(a), C.c_size_t(a.size)), "cl2_write_split_moments_packed")
+
+    def light_share(self, return_map=False):
+        """The share of the frame's luma variance that comes from the light image (t = 1 splats, whose noise is independent between
+        pixels; the rest is camera-image noise, correlated over 3 x 3 pixels): sum rho var_L / sum var_L over the pixels with an
+        estimate.  return_map=True returns (share, rho): rho float32 (H,W), 1 where a pixel has no usable split."""
+        out = (C.c_double * 4)()
+        m = np.empty((self.pixel_height, self.pixel_width), np.float32) if return_map else None
+        self._check(self._L.cl2_light_share(self._h, ptr(m), C.c_size_t(0 if m is None else m.size), out), "cl2_light_share")
+        return (float(out[0]), m) if return_map else float(out[0])
+
     # ---- the error of the filtered picture (cl2_denoise_error, csrc/denoise_error.hpp, DESIGN.md 6.15) ----
     _ERROR_KINDS = {"denoised": 0, "guided": 1}
+    NOISE_MODELS = {"independent": 0, "correlated": 1, "split": 2}
+
+    def _noise_model(self, noise, correlated, who):
+        """None (the old entry points, `correlated` as before) or the model's number for the *_model entry points"""
+        if noise is None:
+            return None
+        if correlated is not None:
+            raise ValueError(f"{who}: give noise= or correlated=, not both")
+        if noise not in self.NOISE_MODELS:
+            raise ValueError(f"{who}: noise is one of {sorted(self.NOISE_MODELS)}, not {noise!r}")
+        return self.NOISE_MODELS[noise]
 
     def denoised_error(self, kind="denoised", floor=None, iterations=None, sigma=None, sigma_depth=None, sigma_albedo=None,
                        probes=1, epsilon=1 / 16, correlated=None, seed=0, return_map=False, return_totals=False,
-                       return_probe=False):
+                       return_probe=False, noise=None):
         """e_dn(floor): relative_error(floor)'s counterpart for the FILTERED picture -- denoised_radiance() (kind "denoised") or
         guided_radiance() ("guided") -- by Monte-Carlo SURE: the filter runs once on the picture and once per probe on a picture
         perturbed by epsilon times the estimated noise, and the response gives the filter's divergence.  render_features() first,
         error tracking on since the last reset.  `sigma` is the filter's sigma_color / sigma_luma; unset filter arguments take
         DENOISE_DEFAULTS / GUIDED_DEFAULTS.  `correlated`: perturb with independent signs (False) or with signs spread like a camera
-        sample over 3 x 3 pixels (True); None takes DENOISED_ERROR_CORRELATED.  `seed` picks the signs: probe k of seed S is probe 0
+        sample over 3 x 3 pixels (True); None takes DENOISED_ERROR_CORRELATED.  `noise` names the model instead: "independent",
+        "correlated", or "split" -- a mix of the two by each pixel's light share (set_split_tracking() before the samples; DESIGN.md
+        6.17); not together with `correlated`.  `seed` picks the signs: probe k of seed S is probe 0
         of seed S + k, and the same arguments give the same bytes.  The extras follow e_dn in this order: return_map the per-pixel
         estimate of the squared luma error, float32 (H,W) (0 uncovered, inf with n < 2; noisy, possibly negative); return_totals
         the eight float64 totals of cl2_denoise_error; return_probe (y', F(y), F(y')) of the last probe, float32 (H,W,3) each."""
@@ -899,15 +947,17 @@ class Renderer:
         sd = d["sigma_depth"] if sigma_depth is None else float(sigma_depth)
         sa = d["sigma_albedo"] if sigma_albedo is None else float(sigma_albedo)
         f = self.ERROR_FLOOR if floor is None else float(floor)
+        model = self._noise_model(noise, correlated, "denoised_error")
         corr = DENOISED_ERROR_CORRELATED if correlated is None else bool(correlated)
         H, W = self.pixel_height, self.pixel_width
         out = (C.c_double * 8)()
         emap = np.empty((H, W), np.float32) if return_map else None
         probe = np.empty((3, H, W, 3), np.float32) if return_probe else None
-        self._check(self._L.cl2_denoise_error(self._h, self._ERROR_KINDS[kind], it, sg, sd, sa, int(probes), float(epsilon), int(corr),
-                                              C.c_uint32(int(seed) & 0xFFFFFFFF), f, out, ptr(emap),
-                                              C.c_size_t(0 if emap is None else emap.size), ptr(probe),
-                                              C.c_size_t(0 if probe is None else probe.size)), "cl2_denoise_error")
+        call, name = (self._L.cl2_denoise_error, "cl2_denoise_error") if model is None else \
+                     (self._L.cl2_denoise_error_model, "cl2_denoise_error_model")
+        self._check(call(self._h, self._ERROR_KINDS[kind], it, sg, sd, sa, int(probes), float(epsilon), int(corr) if model is None else model,
+                         C.c_uint32(int(seed) & 0xFFFFFFFF), f, out, ptr(emap), C.c_size_t(0 if emap is None else emap.size), ptr(probe),
+                         C.c_size_t(0 if probe is None else probe.size)), name)
         extras = []
         if return_map:
             extras.append(emap)
@@ -918,21 +968,24 @@ class Renderer:
         return (float(out[0]), *extras) if extras else float(out[0])
 
     # ---- the fixed filter's scale chosen per pixel (cl2_denoise_select, csrc/denoise_select.hpp) ----
-    def _select_args(self, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes):
+    def _select_args(self, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes,
+                     model=None):
+        """the arguments the select calls share; `model`: the noise model's number in the place of `correlated`"""
         d = self.DENOISE_DEFAULTS
         return (d["iterations"] if iterations is None else int(iterations),
                 d["sigma_color"] if sigma_color is None else float(sigma_color),
                 d["sigma_depth"] if sigma_depth is None else float(sigma_depth),
                 d["sigma_albedo"] if sigma_albedo is None else float(sigma_albedo),
-                int(probes), float(epsilon), int(DENOISED_ERROR_CORRELATED if correlated is None else bool(correlated)),
+                int(probes), float(epsilon),
+                int(DENOISED_ERROR_CORRELATED if correlated is None else bool(correlated)) if model is None else model,
                 C.c_uint32(int(seed) & 0xFFFFFFFF), SELECT_SMOOTH_PASSES if smooth_passes is None else int(smooth_passes))
 
     def selected_radiance(self, iterations=None, sigma_color=None, sigma_depth=None, sigma_albedo=None, probes=1, epsilon=1 / 16,
                           correlated=None, seed=0, smooth_passes=None, floor=None, return_scale=False, return_stats=False,
-                          return_maps=False):
+                          return_maps=False, noise=None):
         """`radiance` after the fixed filter with the number of passes chosen PER PIXEL: float32 (H,W,3), BGR.  One run of
         `iterations` = K passes gives the pictures of denoised_radiance(iterations=0 .. K); denoised_error's Monte-Carlo SURE
-        (probes, epsilon, correlated, seed as there) gives a map of the squared luma error of each; the maps are smoothed by
+        (probes, epsilon, correlated, seed, noise as there) gives a map of the squared luma error of each; the maps are smoothed by
         `smooth_passes` passes of the filter's kernel under its normal, depth and albedo weights, and every pixel takes the level
         whose smoothed estimate is smallest.  render_features() first, error tracking on since the last reset.  Unset arguments
         take DENOISE_DEFAULTS, DENOISED_ERROR_CORRELATED and SELECT_SMOOTH_PASSES; `floor` (ERROR_FLOOR) enters the statistics only.
@@ -941,16 +994,18 @@ class Renderer:
         [6] of the raw picture, [7] the sum of k*; return_maps (m, M), the raw and the smoothed maps, float32 (K+1,H,W) each.
         e_sel is BIASED LOW: it estimates the level that looked best, and a minimum over noisy estimates lies below the estimate
         of any fixed level, on top of the calibration limits of denoised_error.  It is a diagnostic."""
-        a = self._select_args(iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes)
+        model = self._noise_model(noise, correlated, "selected_radiance")
+        a = self._select_args(iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, correlated, seed, smooth_passes, model)
+        call, name = (self._L.cl2_denoise_select, "cl2_denoise_select") if model is None else \
+                     (self._L.cl2_denoise_select_model, "cl2_denoise_select_model")
         f = self.ERROR_FLOOR if floor is None else float(floor)
         H, W = self.pixel_height, self.pixel_width
         pic = np.empty((H, W, 3), np.float32)
         scale = np.empty((H, W), np.int32) if return_scale else None
         maps = np.empty((2, max(a[0], 0) + 1, H, W), np.float32) if return_maps else None
         out = (C.c_double * 8)()
-        self._check(self._L.cl2_denoise_select(self._h, *a, f, ptr(pic), C.c_size_t(pic.size), ptr(scale),
-                                               C.c_size_t(0 if scale is None else scale.size), out, ptr(maps),
-                                               C.c_size_t(0 if maps is None else maps.size), None, C.c_size_t(0)), "cl2_denoise_select")
+        self._check(call(self._h, *a, f, ptr(pic), C.c_size_t(pic.size), ptr(scale), C.c_size_t(0 if scale is None else scale.size), out,
+                         ptr(maps), C.c_size_t(0 if maps is None else maps.size), None, C.c_size_t(0)), name)
         extras = []
         if return_scale:
             extras.append(scale)
@@ -968,15 +1023,21 @@ class Renderer:
     def keep_selected_picture(self, **params):
         """selected_radiance(**params) KEPT in device memory (kind "selected") under keep_picture's rules: a snapshot, nothing is
         copied to the host, a refused call leaves the previous kept picture.  `params`: iterations, sigma_color, sigma_depth,
-        sigma_albedo, probes, epsilon, correlated, seed, smooth_passes."""
-        names = ("iterations", "sigma_color", "sigma_depth", "sigma_albedo", "probes", "epsilon", "correlated", "seed", "smooth_passes")
+        sigma_albedo, probes, epsilon, correlated, seed, smooth_passes, noise."""
+        names = ("iterations", "sigma_color", "sigma_depth", "sigma_albedo", "probes", "epsilon", "correlated", "seed", "smooth_passes",
+                 "noise")
         unknown = sorted(set(params) - set(names))
         if unknown:
             raise TypeError(f"keep_selected_picture takes {sorted(names)}, not {unknown}")
         d = dict(iterations=None, sigma_color=None, sigma_depth=None, sigma_albedo=None, probes=1, epsilon=1 / 16, correlated=None,
                  seed=0, smooth_passes=None)
         d.update(params)
-        self._check(self._L.cl2_keep_selected_picture(self._h, *self._select_args(**d)), "cl2_keep_selected_picture")
+        model = self._noise_model(d.pop("noise", None), d["correlated"], "keep_selected_picture")
+        if model is None:
+            self._check(self._L.cl2_keep_selected_picture(self._h, *self._select_args(**d)), "cl2_keep_selected_picture")
+        else:
+            self._check(self._L.cl2_keep_selected_picture_model(self._h, *self._select_args(**d, model=model)),
+                        "cl2_keep_selected_picture_model")
 
     def best_iterations(self, kind="denoised", candidates=range(0, 6), **params):
         """The pass count among `candidates` whose filtered picture denoised_error(kind, iterations=..., **params) estimates to be
@@ -1002,6 +1063,8 @@ class Renderer:
             raise TypeError("render_until seeds every check with its index")
         if not self.error_tracking:
             self.set_error_tracking(True)
+        if params.get("noise") == "split" and not self.split_tracking:
+            self.set_split_tracking(True)
         try:
             self.features()
         except RendererError:
@@ -1038,7 +1101,10 @@ class Renderer:
         positive (e_dn = 0 by definition, not by convergence) never stops the render.  Not with adaptive=True: the density update
         stays on the raw estimate.  Where the filter removes nearly all of the variance the estimate runs low (at
         10 passes of the 1080p Cornell box e_dn says 0.0086 where the filtered picture's true relative error is 0.0139, and the
-        guided filter's total is negative, so that metric runs to the cap there): leave a margin in `target`."""
+        guided filter's total is negative, so that metric runs to the cap there): leave a margin in `target`.
+        filter_params={"noise": "split"} checks with the split noise model (nearer the truth on that frame, and the
+        guided filter's total turns positive) and turns split tracking on if it is off -- before the first sample, or the rows
+        stay invalid until reset_accumulators()."""
         if metric not in ("picture", "denoised", "guided"):
             raise ValueError(f"render_until: metric is 'picture', 'denoised' or 'guided', not {metric!r}")
         if metric != "picture":
