@@ -77,21 +77,21 @@ __global__ __launch_bounds__(BLOCK) void k_feat_finish(int FB, int samples, floa
     G1[id] = g1;
 }
 
-// ---------------------------------------------------------------- filter
-// Input colour: Renderer.radiance's arithmetic on the packed accumulators [8][FB] (image b, g, r | weight | ...), non-finite
-// values set to 0.  Writes the float4 working buffer, or the packed (H, W, 3) output when no pass follows.
-__global__ __launch_bounds__(BLOCK) void k_denoise_input(int FB, const float* __restrict__ acc, float4* __restrict__ cout,
-                                                         float* __restrict__ out3) {
-    const int p = blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= FB) return;
-    const float w = acc[3 * (size_t)FB + p];
-    float c[3];
+// ---------------------------------------------------------------- the core every picture filter shares
+// (denoise_guided.hpp, denoise_layers.hpp, denoise_error.hpp and denoise_select.hpp build on it; tests/*_reference.py restate it)
+
+// Input colour: Renderer.radiance's arithmetic, row k of `rows` ([3][FB]: b, g, r sums) over the weight w of the pixel, non-finite
+// values set to 0.
+__device__ __forceinline__ void dn_input_colour(const float* __restrict__ rows, size_t FB, size_t p, float w, float (&c)[3]) {
     for (int k = 0; k < 3; k++) {
-        const float x = acc[(size_t)k * FB + p] / w;
+        const float x = rows[k * FB + p] / w;
         c[k] = isfinite(x) ? x : 0.0f;
     }
-    if (out3) { out3[3 * (size_t)p] = c[0]; out3[3 * (size_t)p + 1] = c[1]; out3[3 * (size_t)p + 2] = c[2]; }
-    else cout[p] = make_float4(c[0], c[1], c[2], 0.0f);
+}
+
+// pixel p of a packed (H, W, 3) picture
+__device__ __forceinline__ void dn_store3(float* __restrict__ out3, size_t p, float b, float g, float r) {
+    out3[3 * p] = b; out3[3 * p + 1] = g; out3[3 * p + 2] = r;
 }
 
 __device__ __forceinline__ V3 dn_compress(float4 c) {          // x = c / (1 + luma(c)), luma of camera.py (b, g, r weights)
@@ -104,6 +104,81 @@ __device__ __forceinline__ float dn_pow32(float x) {            // five squaring
     x = x * x; x = x * x; x = x * x; x = x * x; return x * x;
 }
 
+// The feature edge-stop of a tap q seen from the centre (normal n, albedo a, depth zp): ((hh wn) wz) wa with hh = h(dx) h(dy),
+// den_z = (sigma_depth * zp) * (float) step and den_a = sigma_albedo^2.  A filter multiplies its colour or luma term on last.
+__device__ __forceinline__ float dn_feature_weight(float hh, V3 n, V3 a, float zp, float den_z, float den_a, float4 nq, float4 aq) {
+    const float wn = dn_pow32(max_msl(0.0f, dot(n, v3(nq))));
+    const float wz = expf(-fabsf(zp - nq.w) / den_z);
+    const V3 da = a - v3(aq);
+    const float wa = expf(-dot(da, da) / den_a);
+    return ((hh * wn) * wz) * wa;
+}
+
+// Where a pass finds the features of the pixels around its own, (px + ox, py + oy).  LDS_STEP = 1 or 2: those of the workgroup's
+// 16 x 16 pixels and of the halo of two steps around them are staged in LDS first and |ox|, |oy| <= 2 LDS_STEP; LDS_STEP = 0: every
+// tap is two bounds-checked 16-byte global loads.  Staged entries outside the frame are 0: their coverage 0 skips them exactly as
+// the bounds test of the global form does.
+template <int LDS_STEP>
+struct DnTile {
+    static constexpr int T = LDS_STEP ? DN_TILE + 4 * LDS_STEP : 1;      // side of the staged tile
+    int W, H, px, py;
+    const float4 *G0, *G1;
+    float4 *s_n, *s_a;                                                   // T * T entries each
+
+    __device__ __forceinline__ int at(int ox, int oy) const {            // the staged index of a tap
+        return ((int)threadIdx.y + 2 * LDS_STEP + oy) * T + (int)threadIdx.x + 2 * LDS_STEP + ox;
+    }
+    // by every thread of the workgroup, before any leaves: ends in the barrier
+    __device__ __forceinline__ void stage() const {
+        if constexpr (LDS_STEP != 0) {
+            const int x0 = blockIdx.x * DN_TILE - 2 * LDS_STEP, y0 = blockIdx.y * DN_TILE - 2 * LDS_STEP;
+            for (int k = threadIdx.y * DN_TILE + threadIdx.x; k < T * T; k += DN_TILE * DN_TILE) {
+                const int gx = x0 + k % T, gy = y0 + k / T;
+                if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                    const int q = gy * W + gx;
+                    s_n[k] = G0[q]; s_a[k] = G1[q];
+                } else {
+                    s_n[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); s_a[k] = s_n[k];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // normal | depth and albedo | coverage of a tap ((0, 0): the centre); false: outside the frame, skipped
+    __device__ __forceinline__ bool features(int ox, int oy, float4& n, float4& a) const {
+        if constexpr (LDS_STEP != 0) {
+            const int k = at(ox, oy);
+            n = s_n[k]; a = s_a[k];
+        } else {
+            const int qx = px + ox, qy = py + oy;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) return false;
+            const int q = qy * W + qx;
+            n = G0[q]; a = G1[q];
+        }
+        return true;
+    }
+    // the offset of tap d (-2 .. 2) of a pass at `step`: a staged pass runs at step = LDS_STEP
+    __device__ __forceinline__ static int offset(int d, int step) { return d * (LDS_STEP ? LDS_STEP : step); }
+};
+
+// ---------------------------------------------------------------- filter
+// Writes the float4 working buffer from the packed accumulators [8][FB] (image b, g, r | weight | ...), or the packed (H, W, 3)
+// output when no pass follows.
+__global__ __launch_bounds__(BLOCK) void k_denoise_input(int FB, const float* __restrict__ acc, float4* __restrict__ cout,
+                                                         float* __restrict__ out3) {
+    const int p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= FB) return;
+    float c[3];
+    dn_input_colour(acc, (size_t)FB, (size_t)p, acc[3 * (size_t)FB + p], c);
+    if (out3) dn_store3(out3, (size_t)p, c[0], c[1], c[2]);
+    else cout[p] = make_float4(c[0], c[1], c[2], 0.0f);
+}
+
+// k_denoise_pass and k_denoise_guided_pass (denoise_guided.hpp) keep bodies of their own, tile staging and tap weight written out:
+// one body over an edge-stop policy, built on DnTile and dn_feature_weight, gives the same bits but was measured 1 - 4 % slower per
+// launch on the MI355X in every form tried (profiles/r28_README.md), and so was sharing only the stager and the feature weight.
+// The instructions are the same; their schedule is not.  k_layers_denoise_pass and k_ds_smooth do use the shared pieces.
+//
 // One a-trous pass at step `step` (= 2^i).  den_c = sigma_color^2 * 4^-i, den_a = sigma_albedo^2 (host-computed, float32).
 // LDS_STEP = 1 or 2: the workgroup's 16 x 16 pixels and the halo of two steps around them are staged in LDS first (24^2 x 48 B
 // = 27 KB at step 2); LDS_STEP = 0: every tap is three 16-byte global loads.  Staged entries outside the frame carry coverage 0,

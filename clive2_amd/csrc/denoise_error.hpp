@@ -1,7 +1,7 @@
 // denoise_error.hpp -- an estimate of the squared luma error of the FILTERED picture (cl2_denoise or cl2_denoise_guided) by
 // Monte-Carlo SURE: Stein's unbiased risk estimate with the filter's divergence taken from finite differences along random
 // probes (Ramani, Blu, Unser 2008).  It needs only what the handle already holds -- accumulators, the moments of
-// cl2_set_error_tracking, the feature buffers -- and runs the existing filter kernels, untouched, on perturbed inputs.
+// cl2_set_error_tracking, the feature buffers -- and runs the filters' own pass kernels on perturbed inputs.
 //
 // No reference counterpart (the reference stops at the Monte Carlo estimate, src/renderer.py:293-316).  Reads accumulators,
 // moments and features; writes buffers of its own and the filters' shared working buffers.
@@ -82,19 +82,13 @@ __global__ __launch_bounds__(BLOCK) void k_de_input(int FB, int guided, const fl
                                                     float4* __restrict__ Y, float4* __restrict__ A, float* __restrict__ out3) {
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= FB) return;
-    const float w = acc[3 * (size_t)FB + p];
     float c[3];
-    for (int k = 0; k < 3; k++) {
-        const float x = acc[(size_t)k * FB + p] / w;
-        c[k] = isfinite(x) ? x : 0.0f;
-    }
+    dn_input_colour(acc, (size_t)FB, (size_t)p, acc[3 * (size_t)FB + p], c);
     double var[4] = {0, 0, 0, 0}, L = 0.0;
     const int state = err_pixel(acc, mom, (size_t)FB, (size_t)p, var, L);
-    float v = 0.0f;
+    const float v = dng_guide_variance(state, var[3]);
     float a[3] = {0.0f, 0.0f, 0.0f};
-    if (state == 1) v = DNG_VAR_CAP;
-    else if (state == 2) {
-        v = var[3] < (double)DNG_VAR_CAP ? (float)var[3] : DNG_VAR_CAP;
+    if (state == 2) {
         const float s = (float)sqrt((double)v);
         const double se[3] = {sqrt(var[0]), sqrt(var[1]), sqrt(var[2])};
         const double l = err_luma(se[0], se[1], se[2]);
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(BLOCK) void k_de_input(int FB, int guided, const fl
     }
     Y[p] = make_float4(c[0], c[1], c[2], guided ? v : 0.0f);
     A[p] = make_float4(a[0], a[1], a[2], state == 2 ? v : (state == 1 ? -2.0f : -1.0f));
-    if (out3) { out3[3 * (size_t)p] = c[0]; out3[3 * (size_t)p + 1] = c[1]; out3[3 * (size_t)p + 2] = c[2]; }
+    if (out3) dn_store3(out3, (size_t)p, c[0], c[1], c[2]);
 }
 
 __device__ __forceinline__ float de_sign(uint32_t q, uint32_t t) {
@@ -130,18 +124,23 @@ __device__ __forceinline__ float de_correlated_z(int W, int H, int p, uint32_t t
     return (float)((double)num / sqrt((double)den));
 }
 
-// y' = y + (eps z) a
+// y' = y + (eps z) a of pixel p into the working buffer, and into the packed picture when no pass follows
+__device__ __forceinline__ void de_store_perturbed(int p, float ez, const float4* __restrict__ Y, const float4* __restrict__ A,
+                                                   float4* __restrict__ Yp, float* __restrict__ out3) {
+    const float4 y4 = Y[p], a = A[p];
+    const float4 o = make_float4(y4.x + ez * a.x, y4.y + ez * a.y, y4.z + ez * a.z, y4.w);
+    Yp[p] = o;
+    if (out3) dn_store3(out3, (size_t)p, o.x, o.y, o.z);
+}
+
+// the pure modes: z the sign of (p, t), or the correlated field
 __global__ __launch_bounds__(BLOCK) void k_de_perturb(int W, int H, uint32_t t, float eps, int correlated, DeKernel K,
                                                       const float4* __restrict__ Y, const float4* __restrict__ A,
                                                       float4* __restrict__ Yp, float* __restrict__ out3) {
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= W * H) return;
     const float z = correlated ? de_correlated_z(W, H, p, t, K) : de_sign((uint32_t)p, t);
-    const float4 y4 = Y[p], a = A[p];
-    const float ez = eps * z;
-    const float4 o = make_float4(y4.x + ez * a.x, y4.y + ez * a.y, y4.z + ez * a.z, y4.w);
-    Yp[p] = o;
-    if (out3) { out3[3 * (size_t)p] = o.x; out3[3 * (size_t)p + 1] = o.y; out3[3 * (size_t)p + 2] = o.z; }
+    de_store_perturbed(p, eps * z, Y, A, Yp, out3);
 }
 
 // Noise model 2, "split" (error_split.hpp): z_p = cs_p zK_p + cl_p b'_p with zK the correlated field of (p, t)
@@ -158,11 +157,7 @@ __global__ __launch_bounds__(BLOCK) void k_de_perturb_split(int W, int H, uint32
     const float r = rho[p];
     const float cs = (float)sqrt(1.0 - (double)r), cl = (float)sqrt((double)r);
     const float z = cs * de_correlated_z(W, H, p, t, K) + cl * de_sign((uint32_t)p, t ^ 0xA5A5A5A5u);
-    const float4 y4 = Y[p], a = A[p];
-    const float ez = eps * z;
-    const float4 o = make_float4(y4.x + ez * a.x, y4.y + ez * a.y, y4.z + ez * a.z, y4.w);
-    Yp[p] = o;
-    if (out3) { out3[3 * (size_t)p] = o.x; out3[3 * (size_t)p + 1] = o.y; out3[3 * (size_t)p + 2] = o.z; }
+    de_store_perturbed(p, eps * z, Y, A, Yp, out3);
 }
 
 // the colours of a working buffer as a packed (H, W, 3) picture (out_probe's y')
@@ -170,7 +165,7 @@ __global__ __launch_bounds__(BLOCK) void k_de_pack(int FB, const float4* __restr
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= FB) return;
     const float4 c = C4[p];
-    out3[3 * (size_t)p] = c.x; out3[3 * (size_t)p + 1] = c.y; out3[3 * (size_t)p + 2] = c.z;
+    dn_store3(out3, (size_t)p, c.x, c.y, c.z);
 }
 
 constexpr int DE_SUMS = 7;     // out[1..7] of the header

@@ -1,7 +1,7 @@
 // denoise_guided.hpp -- the a-trous filter of denoise.hpp with its colour edge-stop replaced by one that knows the noise: the luma
 // difference of two pixels is compared with the standard error of the centre pixel (the spatial edge-stopping function of SVGF,
 // Schied et al. 2017), taken from the per-pixel variance estimate of error_estimate.hpp.  A second filter beside the fixed one:
-// denoise.hpp, its kernels and its defaults are untouched.
+// the input colour, the packed store and the feature edge-stop it shares with denoise.hpp are defined there.
 //
 // No reference counterpart (the reference stops at the Monte Carlo estimate, src/renderer.py:293-316).  Reads the handle's
 // accumulators, moments and feature buffers; writes buffers of its own.
@@ -33,30 +33,32 @@ namespace cl2 {
 
 constexpr float DNG_VAR_CAP = 0x1p100f;
 
+// the guide variance of a pixel from err_pixel's state and float64 luma variance: v_p of the header
+__device__ __forceinline__ float dng_guide_variance(int state, double var_L) {
+    if (state == 1) return DNG_VAR_CAP;
+    if (state == 2) return var_L < (double)DNG_VAR_CAP ? (float)var_L : DNG_VAR_CAP;      // a NaN takes the cap too
+    return 0.0f;
+}
+
 __global__ __launch_bounds__(BLOCK) void k_denoise_guided_input(int FB, const float* __restrict__ acc, const float* __restrict__ mom,
                                                                 float4* __restrict__ cout, float* __restrict__ out3,
                                                                 float* __restrict__ outv) {
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= FB) return;
-    const float w = acc[3 * (size_t)FB + p];
     float c[3];
-    for (int k = 0; k < 3; k++) {
-        const float x = acc[(size_t)k * FB + p] / w;
-        c[k] = isfinite(x) ? x : 0.0f;
-    }
+    dn_input_colour(acc, (size_t)FB, (size_t)p, acc[3 * (size_t)FB + p], c);
     double var[4] = {0, 0, 0, 0}, L = 0.0;
     const int state = err_pixel(acc, mom, (size_t)FB, (size_t)p, var, L);
-    float v = 0.0f;
-    if (state == 1) v = DNG_VAR_CAP;
-    else if (state == 2) v = var[3] < (double)DNG_VAR_CAP ? (float)var[3] : DNG_VAR_CAP;      // a NaN takes the cap too
+    const float v = dng_guide_variance(state, var[3]);
     if (out3) {
-        out3[3 * (size_t)p] = c[0]; out3[3 * (size_t)p + 1] = c[1]; out3[3 * (size_t)p + 2] = c[2];
+        dn_store3(out3, (size_t)p, c[0], c[1], c[2]);
         if (outv) outv[p] = v;
     } else cout[p] = make_float4(c[0], c[1], c[2], v);
 }
 
 __device__ __forceinline__ float dng_luma(float4 c) { return (c.x * 0.0722f + c.y * 0.7152f) + c.z * 0.2126f; }
 
+// The body is this kernel's own, like k_denoise_pass's: see the note there.
 // One guided pass at step `step` (= 2^i).  den_a = sigma_albedo^2 (host-computed, float32).  LDS_STEP as k_denoise_pass: 1 or 2
 // stage the workgroup's pixels and a halo of two steps (>= 2 pixels, so the 3 x 3 of v comes from the same tile) in LDS;
 // 0 takes every tap from global memory and the 3 x 3 as eight more 4-byte loads each of coverage and v (the centre is at hand).

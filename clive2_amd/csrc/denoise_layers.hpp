@@ -29,16 +29,10 @@ __global__ __launch_bounds__(BLOCK) void k_layers_input(int FB, int l0, int nl, 
     const float w = acc[3 * (size_t)FB + p];
 #pragma unroll 1
     for (int l = l0; l < l0 + nl; l++) {
-        const float* __restrict__ a = lacc + (size_t)3 * l * FB;
         float c[3];
-        for (int k = 0; k < 3; k++) {
-            const float x = a[(size_t)k * FB + p] / w;
-            c[k] = isfinite(x) ? x : 0.0f;
-        }
-        if (out3) {
-            float* __restrict__ o = out3 + 3 * ((size_t)(l - l0) * FB + p);
-            o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
-        } else cout[(size_t)l * FB + p] = make_float4(c[0], c[1], c[2], 0.0f);
+        dn_input_colour(lacc + (size_t)3 * l * FB, (size_t)FB, (size_t)p, w, c);
+        if (out3) dn_store3(out3, (size_t)(l - l0) * FB + p, c[0], c[1], c[2]);
+        else cout[(size_t)l * FB + p] = make_float4(c[0], c[1], c[2], 0.0f);
     }
 }
 
@@ -52,7 +46,7 @@ __global__ __launch_bounds__(DN_TILE * DN_TILE) void k_layers_denoise_pass(int W
                                                                             const float4* __restrict__ cin,
                                                                             const float4* __restrict__ G0, const float4* __restrict__ G1,
                                                                             float4* __restrict__ cout, float* __restrict__ out3) {
-    constexpr int T = LDS_STEP ? DN_TILE + 4 * LDS_STEP : 1;
+    constexpr int T = DnTile<LDS_STEP>::T;
     __shared__ float4 s_n[T * T], s_a[T * T], s_c[T * T];      // s_c = (c.b, c.g, c.r, x.b)
     __shared__ float2 s_x[T * T];                              // (x.g, x.r), x = dn_compress(c)
     const int lx = threadIdx.x, ly = threadIdx.y;
@@ -60,20 +54,12 @@ __global__ __launch_bounds__(DN_TILE * DN_TILE) void k_layers_denoise_pass(int W
     const int x0 = blockIdx.x * DN_TILE - 2 * LDS_STEP, y0 = blockIdx.y * DN_TILE - 2 * LDS_STEP;
     const size_t FB = (size_t)W * H;
     const bool inside = px < W && py < H;
-    if (LDS_STEP) {
-        for (int k = ly * DN_TILE + lx; k < T * T; k += DN_TILE * DN_TILE) {
-            const int gx = x0 + k % T, gy = y0 + k / T;
-            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
-                const int q = gy * W + gx;
-                s_n[k] = G0[q]; s_a[k] = G1[q];
-            } else {
-                s_n[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); s_a[k] = s_n[k];      // coverage 0: skipped like a tap outside
-            }
-        }
-        __syncthreads();
-    } else if (!inside) return;                                 // the global form has no barrier
+    // the features of the tile once, by DnTile; the colours are staged per layer below, with their compressed form
+    const DnTile<LDS_STEP> tile{W, H, px, py, G0, G1, s_n, s_a};
+    tile.stage();
+    if (!LDS_STEP && !inside) return;                           // the global form has no barrier
     const int p = inside ? py * W + px : 0;
-    const int kp = (ly + 2 * LDS_STEP) * T + lx + 2 * LDS_STEP;
+    const int kp = tile.at(0, 0);
 
     // the layer-free part of the 25 tap weights, and the taps that count
     const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
@@ -81,8 +67,7 @@ __global__ __launch_bounds__(DN_TILE * DN_TILE) void k_layers_denoise_pass(int W
     unsigned taps = 0;
     if (inside) {
         float4 np_, ap;
-        if (LDS_STEP) { np_ = s_n[kp]; ap = s_a[kp]; }
-        else { np_ = G0[p]; ap = G1[p]; }
+        tile.features(0, 0, np_, ap);
         if (ap.w != 0.0f) {
             const V3 n = v3(np_), a = v3(ap);
             const float zp = np_.w;
@@ -94,21 +79,9 @@ __global__ __launch_bounds__(DN_TILE * DN_TILE) void k_layers_denoise_pass(int W
                     const int t = (dy + 2) * 5 + dx + 2;
                     f[t] = 0.0f;
                     float4 nq, aq;
-                    if (LDS_STEP) {
-                        const int k = (ly + (2 + dy) * LDS_STEP) * T + lx + (2 + dx) * LDS_STEP;
-                        nq = s_n[k]; aq = s_a[k];
-                    } else {
-                        const int qx = px + dx * step, qy = py + dy * step;
-                        if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
-                        const int q = qy * W + qx;
-                        nq = G0[q]; aq = G1[q];
-                    }
+                    if (!tile.features(tile.offset(dx, step), tile.offset(dy, step), nq, aq)) continue;
                     if (aq.w == 0.0f) continue;
-                    const float wn = dn_pow32(max_msl(0.0f, dot(n, v3(nq))));
-                    const float wz = expf(-fabsf(zp - nq.w) / den_z);
-                    const V3 da = a - v3(aq);
-                    const float wa = expf(-dot(da, da) / den_a);
-                    f[t] = (((h[dx + 2] * h[dy + 2]) * wn) * wz) * wa;
+                    f[t] = dn_feature_weight(h[dx + 2] * h[dy + 2], n, a, zp, den_z, den_a, nq, aq);
                     taps |= 1u << t;
                 }
             }
@@ -153,7 +126,7 @@ __global__ __launch_bounds__(DN_TILE * DN_TILE) void k_layers_denoise_pass(int W
                 float4 cq;
                 V3 xq;
                 if (LDS_STEP) {
-                    const int k = (ly + (2 + dy) * LDS_STEP) * T + lx + (2 + dx) * LDS_STEP;
+                    const int k = tile.at(dx * LDS_STEP, dy * LDS_STEP);
                     cq = s_c[k];
                     const float2 x = s_x[k];
                     xq = v3(cq.w, x.x, x.y);
@@ -170,10 +143,8 @@ __global__ __launch_bounds__(DN_TILE * DN_TILE) void k_layers_denoise_pass(int W
         }
         // as k_denoise_pass: a weight sum that is not greater than 0 keeps the colour; a pixel without coverage has no taps
         if (sw > 0.0f) { o0 = s0 / sw; o1 = s1 / sw; o2 = s2 / sw; }
-        if (out3) {
-            float* __restrict__ o = out3 + 3 * ((size_t)(l - l0) * FB + p);
-            o[0] = o0; o[1] = o1; o[2] = o2;
-        } else cout[(size_t)l * FB + p] = make_float4(o0, o1, o2, 0.0f);
+        if (out3) dn_store3(out3, (size_t)(l - l0) * FB + p, o0, o1, o2);
+        else cout[(size_t)l * FB + p] = make_float4(o0, o1, o2, 0.0f);
     }
 }
 

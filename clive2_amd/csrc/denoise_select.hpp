@@ -5,7 +5,7 @@
 // and the Monte-Carlo SURE terms (denoise_error.hpp) of all K + 1 candidates F_0 = y, F_1, ..., F_K.
 //
 // No reference counterpart (the reference stops at the Monte Carlo estimate, src/renderer.py:293-316).  Reads accumulators, moments
-// and features; writes buffers of its own only.  The existing kernels k_de_input, k_de_perturb and k_denoise_pass run untouched.
+// and features; writes buffers of its own only.  The levels are made by k_de_input, k_de_perturb and k_denoise_pass themselves.
 //
 // Inputs: exactly cl2_denoise_error's for kind 0 -- y and A = (a, code) from k_de_input, y' of probe k from k_de_perturb with
 // t = seed + k, epsilon, correlated.
@@ -23,8 +23,8 @@
 // map, so m_K is that map bit for bit and m_0 is v up to the rounding of y + delta.
 //
 // Smoothing: S = smooth_passes in 0..4 passes of the 5 x 5 B3 kernel at steps 1, 2, 4, ...; a tap's weight is
-//     w = (((h[dx+2] * h[dy+2]) * wn) * wz) * wa
-// with wn, wz, wa formed exactly as in k_denoise_pass (den_z = (sigma_depth * z_p) * (float) step, den_a = sigma_albedo^2) and no
+//     w = dn_feature_weight(h[dx+2] * h[dy+2], ...)
+// of denoise.hpp, the filter's own feature edge-stop (den_z = (sigma_depth * z_p) * (float) step, den_a = sigma_albedo^2), with no
 // colour term.  Skipped taps: outside the frame, feature coverage 0, or a pixel not in state 2.  A centre pixel that is not in
 // state 2 or has coverage 0 keeps its K + 1 values.  The K + 1 maps share every weight: s_j += w * m_j(q), sw += w, row-major over
 // dy, dx like the filter; M_j = s_j / sw, and a weight sum that is not greater than 0 (NaN included) keeps the pixel's K + 1 values.
@@ -128,11 +128,7 @@ __global__ __launch_bounds__(DN_TILE * DN_TILE) void k_ds_smooth(int W, int H, i
                 const float4 aq = G1[q];
                 if (aq.w == 0.0f || ds_state(A[q].w) != 2) continue;
                 const float4 nq = G0[q];
-                const float wn = dn_pow32(max_msl(0.0f, dot(n, v3(nq))));
-                const float wz = expf(-fabsf(zp - nq.w) / den_z);
-                const V3 da = a - v3(aq);
-                const float wa = expf(-dot(da, da) / den_a);
-                w[t] = (((h[dx + 2] * h[dy + 2]) * wn) * wz) * wa;
+                w[t] = dn_feature_weight(h[dx + 2] * h[dy + 2], n, a, zp, den_z, den_a, nq, aq);
                 valid |= 1u << t;
                 sw += w[t];
             }
@@ -177,7 +173,7 @@ __global__ __launch_bounds__(256) void k_ds_select(int FB, int levels, const flo
         }
         const float4 c = L[(size_t)best * FB + p];
         scale[p] = best;
-        out3[3 * p] = c.x; out3[3 * p + 1] = c.y; out3[3 * p + 2] = c.z;
+        dn_store3(out3, p, c.x, c.y, c.z);
         if (state == 0) continue;
         v[1] += 1.0;
         v[6] += (double)best;

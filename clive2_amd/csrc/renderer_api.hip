@@ -978,6 +978,81 @@ int alloc_pixel_state(cl2_renderer* r) {
         if ((r)->density) return fail((r), CL2_E_STATE, "the stage calls have no mapped form: cl2_set_sample_density(NULL) first"); \
     } while (0)
 
+
+// ---------------------------------------------------------------- what the picture filters' entry points share (templates: they
+// cannot stand inside the extern "C" block below, beside their callers)
+// the launch shape of the filters' 16 x 16 kernels
+dim3 dn_tiles(const cl2_renderer* r) { return dim3((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE); }
+const dim3 DN_BLOCK(DN_TILE, DN_TILE);
+
+// Where pass i of a filter reads and writes: float4 working buffers, and on a last pass that leaves a picture the packed (H, W, 3)
+struct PassIO {
+    const float4* cin;
+    float4* cout;
+    float* out3;
+};
+// pass 0 reads `src`, the later ones ping-pong buf[1], buf[0]; the last pass writes the packed picture to `dst`
+struct PingPong {
+    const float4* src;
+    float4* const* buf;
+    float* dst;
+    int iterations;
+    PassIO operator()(int i) const { return {i == 0 ? src : buf[i & 1], buf[(i + 1) & 1], i == iterations - 1 ? dst : nullptr}; }
+};
+// pass i reads level i and writes level i + 1 of `lev` ([levels][FB] float4): every level is kept, none is packed
+struct LevelChain {
+    float4* lev;
+    size_t FB;
+    PassIO operator()(int i) const { return {lev + (size_t)i * FB, lev + (size_t)(i + 1) * FB, nullptr}; }
+};
+
+// The pass loop of every a-trous filter: pass i runs at step 2^i, staged in LDS at steps 1 and 2 (LDS_STEP = step) and from global
+// memory beyond (LDS_STEP = 0).  launch(LDS_STEP as an int_c, i, step, io(i)) launches it.  With iterations = 0 nothing is
+// launched: whoever made the input wrote the picture too.
+template <class IO, class Launch>
+int filter_passes(cl2_renderer* r, int iterations, IO io, Launch launch) {
+    for (int i = 0; i < iterations; i++) {
+        const int step = 1 << i;
+        if (step == 1) launch(int_c<1>{}, i, step, io(i)); else if (step == 2) launch(int_c<2>{}, i, step, io(i)); else launch(int_c<0>{}, i, step, io(i));
+        HIP_TRY(r, hipGetLastError());
+    }
+    return CL2_OK;
+}
+
+// cl2_denoise's passes from a prepared input
+template <class IO>
+int denoise_passes(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, IO io) {
+    const float den_a = sigma_albedo * sigma_albedo;
+    return filter_passes(r, iterations, io, [&](auto LDS_STEP, int i, int step, PassIO b) {
+        const float den_c = std::ldexp(sigma_color * sigma_color, -2 * i);      // sigma_color^2 * 4^-i, exact scaling
+        hipLaunchKernelGGL(k_denoise_pass<LDS_STEP.value>, dn_tiles(r), DN_BLOCK, 0, r->stream, r->W, r->H, step, den_c, sigma_depth, den_a,
+                           b.cin, r->d_g0, r->d_g1, b.cout, b.out3);
+    });
+}
+
+// the guided passes from a prepared input, as denoise_passes; `dvar`: where the last pass leaves its guide variance, or NULL
+template <class IO>
+int guided_passes(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, IO io, float* dvar) {
+    const float den_a = sigma_albedo * sigma_albedo;
+    return filter_passes(r, iterations, io, [&](auto LDS_STEP, int, int step, PassIO b) {
+        hipLaunchKernelGGL(k_denoise_guided_pass<LDS_STEP.value>, dn_tiles(r), DN_BLOCK, 0, r->stream, r->W, r->H, step, sigma_luma, sigma_depth,
+                           den_a, b.cin, r->d_g0, r->d_g1, b.cout, b.out3, dvar);
+    });
+}
+
+// The commit of a call that keeps a picture: `produce(d_pic)` runs the checks and launches that write it.  On CL2_OK the picture
+// is of `kind`; after CL2_E_HIP launches may have written part of it, so there is none; every other refusal comes before the first
+// launch and the previous picture stands.  A buffer made for a call that failed goes again.
+template <class Producer>
+int keep_into_picture(cl2_renderer* r, int kind, Producer produce) {
+    const bool fresh = !r->d_pic;
+    if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
+    const int rc = produce(r->d_pic);
+    if (rc == CL2_OK) r->pic_kind = kind;
+    else if (rc == CL2_E_HIP) r->pic_kind = 0;
+    if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);
+    return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -2402,52 +2477,46 @@ int need_filter_buffers(cl2_renderer* r) {
 }  // namespace
 
 namespace {
-// cl2_denoise after its output checks, shared with cl2_keep_picture: the remaining checks and every launch; the last launch
-// writes the (H, W, 3) picture to `dst` (device memory; nullptr: d_dn_out)
-// the argument and feature checks of cl2_denoise (also cl2_denoise_error's for kind 0)
-int denoise_checks(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo) {
+// The argument checks of every filter call, in the order the callers' tests pin: iterations, then every sigma (`sigma`: the n colour
+// sigmas of cl2_denoise / cl2_denoise_layers, or the luma sigma of the guided filters), then the denominators.  `colour`: the
+// sigmas are colour sigmas, whose square shrinks by 4 per pass and must stay a normal float32 in the last one.
+int filter_arg_checks(cl2_renderer* r, int iterations, const float* sigma, int n, bool colour, float sigma_depth, float sigma_albedo) {
     if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
     auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
-    if (bad(sigma_color) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
+    bool any_bad = bad(sigma_depth) || bad(sigma_albedo);
+    for (int l = 0; l < n; l++) any_bad = any_bad || bad(sigma[l]);
+    if (any_bad) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
     // a denominator below the smallest normal float32 (0 or subnormal) would turn every weight into 0/0 or an untested division
     if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
-    if (iterations >= 1 && std::ldexp(sigma_color * sigma_color, -2 * (iterations - 1)) < FLT_MIN)
-        return fail(r, CL2_E_INVALID, "sigma_color^2 * 4^-(iterations-1) underflows float32");
+    for (int l = 0; colour && l < n; l++)
+        if (iterations >= 1 && std::ldexp(sigma[l] * sigma[l], -2 * (iterations - 1)) < FLT_MIN)
+            return fail(r, CL2_E_INVALID, "sigma_color^2 * 4^-(iterations-1) underflows float32");
+    return CL2_OK;
+}
+
+int need_features(cl2_renderer* r) {
     if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
     return CL2_OK;
 }
 
-// cl2_denoise's passes from a prepared input `src` (pass 0 reads it; the later ones ping-pong d_dn[1], d_dn[0]); the last launch
-// writes the (H, W, 3) picture to `dst`.  With iterations = 0 nothing is launched: whoever made `src` wrote `dst` too.
-int denoise_passes(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, const float4* src,
-                   float* dst) {
-    hipStream_t st = r->stream;
-    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
-    const float den_a = sigma_albedo * sigma_albedo;
-    for (int i = 0; i < iterations; i++) {
-        const int step = 1 << i;
-        const float den_c = std::ldexp(sigma_color * sigma_color, -2 * i);      // sigma_color^2 * 4^-i, exact scaling
-        const float4* cin = i == 0 ? src : r->d_dn[i & 1];
-        float4* cout = r->d_dn[(i + 1) & 1];
-        float* out3 = i == iterations - 1 ? dst : nullptr;
-        auto pass = [&](auto LDS_STEP) {
-            hipLaunchKernelGGL(k_denoise_pass<LDS_STEP.value>, grid, block, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3);
-        };
-        if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
-        HIP_TRY(r, hipGetLastError());
-    }
-    return CL2_OK;
+// the argument and feature checks of cl2_denoise (`colour`; also cl2_denoise_error's for kind 0) and of cl2_denoise_guided /
+// cl2_denoise_robust (also cl2_denoise_error's for kind 1)
+int filter_checks(cl2_renderer* r, int iterations, float sigma, bool colour, float sigma_depth, float sigma_albedo) {
+    TRY(filter_arg_checks(r, iterations, &sigma, 1, colour, sigma_depth, sigma_albedo));
+    return need_features(r);
 }
 
+// cl2_denoise after its output checks, shared with cl2_keep_picture: the remaining checks and every launch; the last launch
+// writes the (H, W, 3) picture to `dst` (device memory; nullptr: d_dn_out)
 int run_denoise(cl2_renderer* r, int iterations, float sigma_color, float sigma_depth, float sigma_albedo, float* dst) {
-    TRY(denoise_checks(r, iterations, sigma_color, sigma_depth, sigma_albedo));
+    TRY(filter_checks(r, iterations, sigma_color, true, sigma_depth, sigma_albedo));
     const size_t FB = (size_t)r->FB;
     TRY(need_filter_buffers(r));
     if (!dst) dst = r->d_dn_out;
     hipLaunchKernelGGL(k_denoise_input, dim3(grid_for(FB)), dim3(BLOCK), 0, r->stream, r->FB, (const float*)r->d_acc, r->d_dn[0],
                        iterations == 0 ? dst : (float*)nullptr);
     HIP_TRY(r, hipGetLastError());
-    TRY(denoise_passes(r, iterations, sigma_color, sigma_depth, sigma_albedo, r->d_dn[0], dst));
+    TRY(denoise_passes(r, iterations, sigma_color, sigma_depth, sigma_albedo, PingPong{r->d_dn[0], r->d_dn, dst, iterations}));
     return drain(r);
 }
 }  // namespace
@@ -2701,39 +2770,9 @@ namespace {
 // cl2_denoise_guided / cl2_denoise_robust after their output checks, shared with cl2_keep_picture: the remaining checks and every
 // launch.  `robust`: the input pass reads the buckets (cl2_denoise_robust) instead of accumulators and moments.  `want_var`: the
 // guide variance is carried into d_dn_var.  The last launch writes the (H, W, 3) picture to `dst` (device memory; nullptr: d_dn_out).
-// the argument and feature checks of cl2_denoise_guided / cl2_denoise_robust (also cl2_denoise_error's for kind 1)
-int guided_checks(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo) {
-    if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
-    auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
-    if (bad(sigma_luma) || bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
-    if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
-    if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
-    return CL2_OK;
-}
-
-// the guided passes from a prepared input `src`, as denoise_passes; `dvar`: where the last pass leaves its guide variance, or NULL
-int guided_passes(cl2_renderer* r, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, const float4* src,
-                  float* dst, float* dvar) {
-    hipStream_t st = r->stream;
-    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
-    const float den_a = sigma_albedo * sigma_albedo;
-    for (int i = 0; i < iterations; i++) {
-        const int step = 1 << i;
-        const float4* cin = i == 0 ? src : r->d_dn[i & 1];
-        float4* cout = r->d_dn[(i + 1) & 1];
-        float* out3 = i == iterations - 1 ? dst : nullptr;
-        auto pass = [&](auto LDS_STEP) {
-            hipLaunchKernelGGL(k_denoise_guided_pass<LDS_STEP.value>, grid, block, 0, st, r->W, r->H, step, sigma_luma, sigma_depth, den_a, cin, r->d_g0, r->d_g1, cout, out3, dvar);
-        };
-        if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
-        HIP_TRY(r, hipGetLastError());
-    }
-    return CL2_OK;
-}
-
 int run_guided(cl2_renderer* r, bool robust, int iterations, float sigma_luma, float sigma_depth, float sigma_albedo, bool want_var,
                float* dst) {
-    TRY(guided_checks(r, iterations, sigma_luma, sigma_depth, sigma_albedo));
+    TRY(filter_checks(r, iterations, sigma_luma, false, sigma_depth, sigma_albedo));
     if (robust)
         TRY(robust_ready(r));
     else
@@ -2751,7 +2790,7 @@ int run_guided(cl2_renderer* r, bool robust, int iterations, float sigma_luma, f
         hipLaunchKernelGGL(k_denoise_guided_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, (const float*)r->d_acc,
                            (const float*)r->d_mom, r->d_dn[0], iterations == 0 ? dst : (float*)nullptr, dvar);
     HIP_TRY(r, hipGetLastError());
-    TRY(guided_passes(r, iterations, sigma_luma, sigma_depth, sigma_albedo, r->d_dn[0], dst, dvar));
+    TRY(guided_passes(r, iterations, sigma_luma, sigma_depth, sigma_albedo, PingPong{r->d_dn[0], r->d_dn, dst, iterations}, dvar));
     return drain(r);
 }
 
@@ -2792,6 +2831,30 @@ int check_noise_model(cl2_renderer* r, int model, bool legacy) {
     if (legacy) return (model < 0 || model > 1) ? fail(r, CL2_E_INVALID, "correlated must be 0 or 1") : CL2_OK;
     return (model < 0 || model > 2) ? fail(r, CL2_E_INVALID, "noise_model must be 0 (independent), 1 (correlated) or 2 (split)") : CL2_OK;
 }
+// the arguments every SURE call shares, in the order their tests pin
+int sure_arg_checks(cl2_renderer* r, int probes, float epsilon, int model, bool legacy, double floor) {
+    if (probes < 1 || probes > 16) return fail(r, CL2_E_INVALID, "probes must be in 1..16");
+    if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return fail(r, CL2_E_INVALID, "epsilon must be positive and finite");
+    TRY(check_noise_model(r, model, legacy));
+    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
+    return CL2_OK;
+}
+// The mean reconstruction weights of a camera sample, in float64 with erf (denoise_error.hpp).  `correlated`: the noise model reads
+// them (1 and 2), so weights that are not positive and finite are refused; the independent model carries them unread.
+int reconstruction_weights(cl2_renderer* r, bool correlated, DeKernel& K) {
+    const float ppw = r->cam.phys_width / r->cam.pixel_width, pph = r->cam.phys_height / r->cam.pixel_height;
+    const double s2 = (double)ppw * ppw + (double)pph * pph;
+    const double c[2] = {s2 / (2.0 * ppw * ppw), s2 / (2.0 * pph * pph)};
+    for (int a = 0; a < 2; a++)
+        for (int i = -1; i <= 1; i++) {
+            const double q = std::sqrt(c[a]);
+            const double k = 0.5 * std::sqrt(c[a] * 3.14159265358979323846) * (std::erf((1.0 - i) / q) - std::erf(-i / q));
+            if (correlated && !(k > 0.0 && std::isfinite(k)))
+                return fail(r, CL2_E_STATE, "the camera's pixel sizes give no reconstruction weights");
+            (a == 0 ? K.kx : K.ky)[i + 1] = (float)k;
+        }
+    return CL2_OK;
+}
 int need_split_rows(cl2_renderer* r) {
     if (!r->d_smom) return fail(r, CL2_E_STATE, "split tracking is off (cl2_set_split_tracking)");
     if (!r->smom_valid)
@@ -2823,34 +2886,16 @@ int run_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, fl
     STAGE_PROLOGUE(r);
     if (!out) return fail(r, CL2_E_INVALID, "NULL output");
     if (kind < 0 || kind > 1) return fail(r, CL2_E_INVALID, "denoise error: kind 0 (cl2_denoise) or 1 (cl2_denoise_guided)");
-    if (probes < 1 || probes > 16) return fail(r, CL2_E_INVALID, "probes must be in 1..16");
-    if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return fail(r, CL2_E_INVALID, "epsilon must be positive and finite");
-    TRY(check_noise_model(r, model, legacy));
-    const int correlated = model != 0;   // the reconstruction weights are needed
-    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
+    TRY(sure_arg_checks(r, probes, epsilon, model, legacy, floor));
     const size_t FB = (size_t)r->FB;
     if (out_map ? n_map != FB : n_map != 0) return fail(r, CL2_E_INVALID, "the error map must hold W*H floats (or be NULL with n_map 0)");
     if (out_probe ? n_probe != 9 * FB : n_probe != 0)
         return fail(r, CL2_E_INVALID, "the probe pictures must hold 3*(3*W*H) floats (or be NULL with n_probe 0)");
-    if (kind == 0) TRY(denoise_checks(r, iterations, sigma, sigma_depth, sigma_albedo));
-    else TRY(guided_checks(r, iterations, sigma, sigma_depth, sigma_albedo));
+    TRY(filter_checks(r, iterations, sigma, kind == 0, sigma_depth, sigma_albedo));
     TRY(need_moments(r));
     if (model == 2) TRY(need_split_rows(r));
-    // the mean reconstruction weights of a camera sample, in float64 with erf (denoise_error.hpp)
     DeKernel K;
-    {
-        const float ppw = r->cam.phys_width / r->cam.pixel_width, pph = r->cam.phys_height / r->cam.pixel_height;
-        const double s2 = (double)ppw * ppw + (double)pph * pph;
-        const double c[2] = {s2 / (2.0 * ppw * ppw), s2 / (2.0 * pph * pph)};
-        for (int a = 0; a < 2; a++)
-            for (int i = -1; i <= 1; i++) {
-                const double q = std::sqrt(c[a]);
-                const double k = 0.5 * std::sqrt(c[a] * 3.14159265358979323846) * (std::erf((1.0 - i) / q) - std::erf(-i / q));
-                if (correlated && !(k > 0.0 && std::isfinite(k)))
-                    return fail(r, CL2_E_STATE, "the camera's pixel sizes give no reconstruction weights");
-                (a == 0 ? K.kx : K.ky)[i + 1] = (float)k;
-            }
-    }
+    TRY(reconstruction_weights(r, model != 0, K));
     TRY(drain(r));
     TRY(need_filter_buffers(r));
     if (model == 2 && !r->d_de_rho) TRY(dev_alloc(r, &r->d_de_rho, FB));
@@ -2868,8 +2913,9 @@ int run_denoise_error(cl2_renderer* r, int kind, int iterations, float sigma, fl
     double* const res = partial + (size_t)DE_SUMS * ERR_BLOCKS;
     hipStream_t st = r->stream;
     auto passes = [&](const float4* src, float* dst) {
-        return kind == 0 ? denoise_passes(r, iterations, sigma, sigma_depth, sigma_albedo, src, dst)
-                         : guided_passes(r, iterations, sigma, sigma_depth, sigma_albedo, src, dst, nullptr);
+        const PingPong io{src, r->d_dn, dst, iterations};
+        return kind == 0 ? denoise_passes(r, iterations, sigma, sigma_depth, sigma_albedo, io)
+                         : guided_passes(r, iterations, sigma, sigma_depth, sigma_albedo, io, nullptr);
     };
     hipLaunchKernelGGL(k_de_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, kind, (const float*)r->d_acc, (const float*)r->d_mom,
                        r->d_de_y, r->d_de_a, iterations == 0 ? r->d_de_fy : (float*)nullptr);
@@ -2938,17 +2984,11 @@ int cl2_keep_picture(cl2_renderer* r, int kind, int iterations, float sigma, flo
         TRY(robust_ready(r));
     else
         STAGE_PROLOGUE(r);
-    const bool fresh = !r->d_pic;
-    if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
-    int rc;
-    if (kind == 1) rc = run_denoise(r, iterations, sigma, sigma_depth, sigma_albedo, r->d_pic);
-    else if (kind == 3) rc = run_robust(r, r->d_pic, nullptr);
-    else rc = run_guided(r, kind == 4, iterations, sigma, sigma_depth, sigma_albedo, false, r->d_pic);
-    if (rc == CL2_OK) r->pic_kind = kind;
-    else if (rc == CL2_E_HIP) r->pic_kind = 0;                    // launches may have written part of it
-    // every other refusal comes before the first launch: the previous picture stands; a buffer made for this call goes again
-    if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);
-    return rc;
+    return keep_into_picture(r, kind, [&](float* pic) {
+        if (kind == 1) return run_denoise(r, iterations, sigma, sigma_depth, sigma_albedo, pic);
+        if (kind == 3) return run_robust(r, pic, nullptr);
+        return run_guided(r, kind == 4, iterations, sigma, sigma_depth, sigma_albedo, false, pic);
+    });
 }
 
 int cl2_kept_picture(const cl2_renderer* r) { return r ? r->pic_kind : 0; }
@@ -2973,17 +3013,9 @@ int need_layer_filter_buffers(cl2_renderer* r) {
 int run_denoise_layers(cl2_renderer* r, int layer, int iterations, const float* sigma_color, float sigma_depth, float sigma_albedo,
                        bool want_sum, float* dst, const float** layers_out, const float** sum_out) {
     const int L = r->n_layers;
-    if (iterations < 0 || iterations > 12) return fail(r, CL2_E_INVALID, "iterations must be in 0..12");
-    auto bad = [](float x) { return !(x > 0.0f) || !std::isfinite(x); };
-    if (bad(sigma_depth) || bad(sigma_albedo)) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
-    for (int l = 0; l < L; l++)
-        if (bad(sigma_color[l])) return fail(r, CL2_E_INVALID, "sigmas must be positive and finite");
-    if (sigma_albedo * sigma_albedo < FLT_MIN) return fail(r, CL2_E_INVALID, "sigma_albedo^2 underflows float32");
-    for (int l = 0; l < L; l++)
-        if (iterations >= 1 && std::ldexp(sigma_color[l] * sigma_color[l], -2 * (iterations - 1)) < FLT_MIN)
-            return fail(r, CL2_E_INVALID, "sigma_color^2 * 4^-(iterations-1) underflows float32");
+    TRY(filter_arg_checks(r, iterations, sigma_color, L, true, sigma_depth, sigma_albedo));
     TRY(need_valid_layers(r));
-    if (!r->features_valid) return fail(r, CL2_E_STATE, "no features for the current scene (call cl2_render_features first)");
+    TRY(need_features(r));
     TRY(need_layer_filter_buffers(r));
     const size_t FB = (size_t)r->FB;
     const int l0 = layer < 0 ? 0 : layer, nl = layer < 0 ? L : 1;
@@ -2992,22 +3024,13 @@ int run_denoise_layers(cl2_renderer* r, int layer, int iterations, const float* 
     hipLaunchKernelGGL(k_layers_input, dim3(grid_for(FB)), dim3(BLOCK), 0, st, r->FB, l0, nl, (const float*)r->d_acc,
                        (const float*)r->d_lacc, r->d_ldn[0], iterations == 0 ? packed : (float*)nullptr);
     HIP_TRY(r, hipGetLastError());
-    const dim3 grid((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), block(DN_TILE, DN_TILE);
     const float den_a = sigma_albedo * sigma_albedo;
-    for (int i = 0; i < iterations; i++) {
-        const int step = 1 << i;
+    TRY(filter_passes(r, iterations, PingPong{r->d_ldn[0], r->d_ldn, packed, iterations}, [&](auto LDS_STEP, int i, int step, PassIO b) {
         LayerDen den{};
-        for (int l = 0; l < L; l++) den.den_c[l] = std::ldexp(sigma_color[l] * sigma_color[l], -2 * i);      // as run_denoise
-        const float4* cin = r->d_ldn[i & 1];
-        float4* cout = r->d_ldn[(i + 1) & 1];
-        float* out3 = i == iterations - 1 ? packed : nullptr;
-        auto pass = [&](auto LDS_STEP) {
-            hipLaunchKernelGGL(k_layers_denoise_pass<LDS_STEP.value>, grid, block, 0, st, r->W, r->H, step, l0, nl, den, sigma_depth, den_a, cin,
-                               r->d_g0, r->d_g1, cout, out3);
-        };
-        if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
-        HIP_TRY(r, hipGetLastError());
-    }
+        for (int l = 0; l < L; l++) den.den_c[l] = std::ldexp(sigma_color[l] * sigma_color[l], -2 * i);      // as denoise_passes
+        hipLaunchKernelGGL(k_layers_denoise_pass<LDS_STEP.value>, dn_tiles(r), DN_BLOCK, 0, st, r->W, r->H, step, l0, nl, den, sigma_depth, den_a,
+                           b.cin, r->d_g0, r->d_g1, b.cout, b.out3);
+    }));
     if (layers_out) *layers_out = packed;
     if (layer < 0 && want_sum) {
         // the packed pictures fill 3/4 of their buffer; the other buffer was last read by the launch that wrote them
@@ -3043,14 +3066,9 @@ int cl2_keep_layer_picture(cl2_renderer* r, int layer, int iterations, const flo
     if (r->n_layers == 0) return fail(r, CL2_E_STATE, "no layer table is set (cl2_set_layers)");
     if (layer < -1 || layer >= r->n_layers) return fail(r, CL2_E_INVALID, "kept layer picture: a layer of the table (0..n_layers-1) or -1 for the sum");
     TRY(drain(r));
-    const bool fresh = !r->d_pic;
-    if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
-    const int rc = run_denoise_layers(r, layer, iterations, sigma_color, sigma_depth, sigma_albedo, true, r->d_pic, nullptr, nullptr);
-    if (rc == CL2_OK) r->pic_kind = layer < 0 ? 7 : 6;
-    else if (rc == CL2_E_HIP) r->pic_kind = 0;                    // launches may have written part of it
-    // every other refusal comes before the first launch: the previous picture stands; a buffer made for this call goes again
-    if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);
-    return rc;
+    return keep_into_picture(r, layer < 0 ? 7 : 6, [&](float* pic) {
+        return run_denoise_layers(r, layer, iterations, sigma_color, sigma_depth, sigma_albedo, true, pic, nullptr, nullptr);
+    });
 }
 
 // ---------------------------------------------------------------- the filter's scale per pixel (csrc/denoise_select.hpp, DESIGN 6.16;
@@ -3080,29 +3098,12 @@ int run_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_d
                int model, bool legacy, uint32_t seed, int smooth_passes, double floor, float* dst, const float** maps_out) {
     if (iterations < 1 || iterations > 12) return fail(r, CL2_E_INVALID, "scale selection: iterations must be in 1..12");
     if (smooth_passes < 0 || smooth_passes > DS_MAX_SMOOTH) return fail(r, CL2_E_INVALID, "smooth_passes must be in 0..4");
-    if (probes < 1 || probes > 16) return fail(r, CL2_E_INVALID, "probes must be in 1..16");
-    if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return fail(r, CL2_E_INVALID, "epsilon must be positive and finite");
-    TRY(check_noise_model(r, model, legacy));
-    const int correlated = model != 0;   // the reconstruction weights are needed
-    if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(r, CL2_E_INVALID, "floor must be >= 0 and finite");
-    TRY(denoise_checks(r, iterations, sigma_color, sigma_depth, sigma_albedo));
+    TRY(sure_arg_checks(r, probes, epsilon, model, legacy, floor));
+    TRY(filter_checks(r, iterations, sigma_color, true, sigma_depth, sigma_albedo));
     TRY(need_moments(r));
     if (model == 2) TRY(need_split_rows(r));
-    // the mean reconstruction weights of a camera sample, as cl2_denoise_error forms them (denoise_error.hpp)
     DeKernel K;
-    {
-        const float ppw = r->cam.phys_width / r->cam.pixel_width, pph = r->cam.phys_height / r->cam.pixel_height;
-        const double s2 = (double)ppw * ppw + (double)pph * pph;
-        const double c[2] = {s2 / (2.0 * ppw * ppw), s2 / (2.0 * pph * pph)};
-        for (int a = 0; a < 2; a++)
-            for (int i = -1; i <= 1; i++) {
-                const double q = std::sqrt(c[a]);
-                const double k = 0.5 * std::sqrt(c[a] * 3.14159265358979323846) * (std::erf((1.0 - i) / q) - std::erf(-i / q));
-                if (correlated && !(k > 0.0 && std::isfinite(k)))
-                    return fail(r, CL2_E_STATE, "the camera's pixel sizes give no reconstruction weights");
-                (a == 0 ? K.kx : K.ky)[i + 1] = (float)k;
-            }
-    }
+    TRY(reconstruction_weights(r, model != 0, K));
     TRY(drain(r));
     const int levels = iterations + 1;
     TRY(need_select_buffers(r, levels));
@@ -3115,24 +3116,8 @@ int run_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_d
     float* const maps[3] = {r->d_ds_map, r->d_ds_map + (size_t)r->ds_levels * FB, r->d_ds_map + 2 * (size_t)r->ds_levels * FB};
     if (!dst) dst = r->d_ds_out;
     hipStream_t st = r->stream;
-    const dim3 tiles((r->W + DN_TILE - 1) / DN_TILE, (r->H + DN_TILE - 1) / DN_TILE), tile(DN_TILE, DN_TILE);
-    const float den_a = sigma_albedo * sigma_albedo;
-    // denoise_passes' launches, every pass into the next level's float4 buffer
-    auto passes = [&](float4* lev) {
-        for (int i = 0; i < iterations; i++) {
-            const int step = 1 << i;
-            const float den_c = std::ldexp(sigma_color * sigma_color, -2 * i);
-            const float4* cin = lev + (size_t)i * FB;
-            float4* cout = lev + (size_t)(i + 1) * FB;
-            auto pass = [&](auto LDS_STEP) {
-                hipLaunchKernelGGL(k_denoise_pass<LDS_STEP.value>, tiles, tile, 0, st, r->W, r->H, step, den_c, sigma_depth, den_a, cin,
-                                   r->d_g0, r->d_g1, cout, (float*)nullptr);
-            };
-            if (step == 1) pass(int_c<1>{}); else if (step == 2) pass(int_c<2>{}); else pass(int_c<0>{});
-            HIP_TRY(r, hipGetLastError());
-        }
-        return CL2_OK;
-    };
+    // cl2_denoise's passes, every one into the next level's float4 buffer
+    auto passes = [&](float4* lev) { return denoise_passes(r, iterations, sigma_color, sigma_depth, sigma_albedo, LevelChain{lev, FB}); };
     const int blocks = grid_for(FB);
     hipLaunchKernelGGL(k_de_input, dim3(blocks), dim3(BLOCK), 0, st, r->FB, 0, (const float*)r->d_acc, (const float*)r->d_mom, L,
                        r->d_ds_a, (float*)nullptr);
@@ -3155,7 +3140,7 @@ int run_select(cl2_renderer* r, int iterations, float sigma_color, float sigma_d
     const float* M = maps[0];
     for (int s = 0; s < smooth_passes; s++) {
         float* const to = maps[1 + (s & 1)];
-        hipLaunchKernelGGL(k_ds_smooth, tiles, tile, 0, st, r->W, r->H, levels, 1 << s, sigma_depth, den_a, M, (const float4*)r->d_g0,
+        hipLaunchKernelGGL(k_ds_smooth, dn_tiles(r), DN_BLOCK, 0, st, r->W, r->H, levels, 1 << s, sigma_depth, sigma_albedo * sigma_albedo, M, (const float4*)r->d_g0,
                            (const float4*)r->d_g1, (const float4*)r->d_ds_a, to);
         HIP_TRY(r, hipGetLastError());
         M = to;
@@ -3214,16 +3199,11 @@ int keep_selected_call(cl2_renderer* r, int iterations, float sigma_color, float
                        float epsilon, int model, bool legacy, uint32_t seed, int smooth_passes) {
     STAGE_PROLOGUE(r);
     TRY(drain(r));
-    const bool fresh = !r->d_pic;
-    if (fresh) TRY(dev_alloc(r, &r->d_pic, 3 * (size_t)r->FB));
     // the totals are formed with floor 0 and stay on the device: only the picture is kept
-    const int rc = run_select(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, model, legacy, seed, smooth_passes, 0.0,
-                              r->d_pic, nullptr);
-    if (rc == CL2_OK) r->pic_kind = 8;
-    else if (rc == CL2_E_HIP) r->pic_kind = 0;                    // launches may have written part of it
-    // every other refusal comes before the first launch: the previous picture stands; a buffer made for this call goes again
-    if (rc != CL2_OK && fresh) dev_free(r, r->d_pic);
-    return rc;
+    return keep_into_picture(r, 8, [&](float* pic) {
+        return run_select(r, iterations, sigma_color, sigma_depth, sigma_albedo, probes, epsilon, model, legacy, seed, smooth_passes, 0.0, pic,
+                          nullptr);
+    });
 }
 }  // namespace
 

@@ -56,39 +56,43 @@ __device__ __forceinline__ float rb_scrub(float x) {   // scrub (kernels.hpp)
     return (x != x || __builtin_isinf(x)) ? 0.0f : x;
 }
 
-// One thread per pixel.  The keys and ranks live in registers: every loop over the buckets runs to ROBUST_MAX_BUCKETS with its
-// index known at compile time and the test k < M inside, so nothing is indexed at run time and nothing goes to scratch.
-// out (H, W, 3) float32; stats NULL or (H, W, 2) float32 = G, c.
-__global__ __launch_bounds__(256) void k_robust_picture(size_t FB, int M, const float* __restrict__ bkt, float* __restrict__ out,
-                                                        float2* __restrict__ stats) {
-    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= FB) return;
+// The trim of one pixel: keys, ranks, Gini G and trim count c as the header states them.  Everything lives in registers: every loop
+// over the buckets runs to ROBUST_MAX_BUCKETS with its index known at compile time and the test k < M inside, so nothing is indexed
+// at run time and nothing goes to scratch -- in rb_trim and in every loop a caller writes over key[] and rank[].
+struct RbTrim {
+    double key[ROBUST_MAX_BUCKETS];       // 0.0 for an invalid bucket
+    int rank[ROBUST_MAX_BUCKETS];         // 0-based; an invalid bucket has none: ROBUST_MAX_BUCKETS
+    unsigned valid;                       // bit k: bucket k is valid
+    int m, c;
+    double G;
+    __device__ __forceinline__ bool kept(int k) const { return rank[k] >= c && rank[k] < m - c; }      // invalid: rank >= m
+};
+
+__device__ __forceinline__ void rb_trim(const float* __restrict__ bkt, int M, size_t FB, size_t p, RbTrim& t) {
     constexpr int MAXM = ROBUST_MAX_BUCKETS;
-    double key[MAXM];
-    unsigned valid = 0;
+    t.valid = 0;
     int m = 0;
 #pragma unroll
     for (int k = 0; k < MAXM; k++) {
-        key[k] = 0.0;
+        t.key[k] = 0.0;
         if (k < M) {
             const float* b = bkt + (size_t)(4 * k) * FB + p;
             const double W = (double)b[3 * FB];
             if (W > 0.0 && W < __builtin_inf()) {
                 const double q = rb_luma((double)b[0] / W, (double)b[FB] / W, (double)b[2 * FB] / W);
-                key[k] = q != q ? __builtin_inf() : q;
-                valid |= 1u << k;
+                t.key[k] = q != q ? __builtin_inf() : q;
+                t.valid |= 1u << k;
                 m++;
             }
         }
     }
-    int rank[MAXM];
 #pragma unroll
     for (int k = 0; k < MAXM; k++) {
         int n = 0;
 #pragma unroll
         for (int j = 0; j < MAXM; j++)
-            if (j != k && ((valid >> j) & 1u) && (key[j] < key[k] || (key[j] == key[k] && j < k))) n++;
-        rank[k] = ((valid >> k) & 1u) ? n : MAXM;                 // 0-based; an invalid bucket has no rank
+            if (j != k && ((t.valid >> j) & 1u) && (t.key[j] < t.key[k] || (t.key[j] == t.key[k] && j < k))) n++;
+        t.rank[k] = ((t.valid >> k) & 1u) ? n : MAXM;
     }
     double S = 0.0, N = 0.0;
 #pragma unroll
@@ -96,7 +100,7 @@ __global__ __launch_bounds__(256) void k_robust_picture(size_t FB, int M, const 
         if (j < m) {
             double q = 0.0;
 #pragma unroll
-            for (int k = 0; k < MAXM; k++) q = rank[k] == j ? key[k] : q;
+            for (int k = 0; k < MAXM; k++) q = t.rank[k] == j ? t.key[k] : q;
             const double v = q > 0.0 ? q : 0.0;
             S += v;
             N += (double)(2 * (j + 1) - m - 1) * v;
@@ -111,11 +115,17 @@ __global__ __launch_bounds__(256) void k_robust_picture(size_t FB, int M, const 
     }
     int c = (int)floor(G * (double)m / 2.0);
     const int cmax = m > 0 ? (m - 1) / 2 : 0;
-    c = c < cmax ? c : cmax;
+    t.c = c < cmax ? c : cmax;
+    t.m = m;
+    t.G = G;
+}
+
+// the pixel of the robust picture: float32 sums over the kept buckets in ascending bucket index, divided and scrubbed; 0 at m = 0
+__device__ __forceinline__ void rb_kept_colour(const float* __restrict__ bkt, size_t FB, size_t p, const RbTrim& t, float (&o)[3]) {
     float X0 = 0.0f, X1 = 0.0f, X2 = 0.0f, Wt = 0.0f;
 #pragma unroll
-    for (int k = 0; k < MAXM; k++) {
-        if (rank[k] >= c && rank[k] < m - c) {                    // invalid: rank MAXM >= m
+    for (int k = 0; k < ROBUST_MAX_BUCKETS; k++) {
+        if (t.kept(k)) {
             const float* b = bkt + (size_t)(4 * k) * FB + p;
             X0 += b[0];
             X1 += b[FB];
@@ -123,12 +133,23 @@ __global__ __launch_bounds__(256) void k_robust_picture(size_t FB, int M, const 
             Wt += b[3 * FB];
         }
     }
-    float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
-    if (m > 0) { o0 = rb_scrub(X0 / Wt); o1 = rb_scrub(X1 / Wt); o2 = rb_scrub(X2 / Wt); }
-    out[3 * p] = o0;
-    out[3 * p + 1] = o1;
-    out[3 * p + 2] = o2;
-    if (stats) stats[p] = make_float2((float)G, (float)c);
+    o[0] = o[1] = o[2] = 0.0f;
+    if (t.m > 0) { o[0] = rb_scrub(X0 / Wt); o[1] = rb_scrub(X1 / Wt); o[2] = rb_scrub(X2 / Wt); }
+}
+
+// One thread per pixel.  out (H, W, 3) float32; stats NULL or (H, W, 2) float32 = G, c.
+__global__ __launch_bounds__(256) void k_robust_picture(size_t FB, int M, const float* __restrict__ bkt, float* __restrict__ out,
+                                                        float2* __restrict__ stats) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= FB) return;
+    RbTrim t;
+    rb_trim(bkt, M, FB, p, t);
+    float o[3];
+    rb_kept_colour(bkt, FB, p, t, o);
+    out[3 * p] = o[0];
+    out[3 * p + 1] = o[1];
+    out[3 * p + 2] = o[2];
+    if (stats) stats[p] = make_float2((float)t.G, (float)t.c);
 }
 
 }  // namespace cl2
